@@ -13,6 +13,13 @@ Launched by the driver as:
 One step = processing FRAMES_PER_STEP 1080p frames per GPU through the
 engine pipeline (load -> SVC GPU decode -> op(s) -> save). Weak scaling:
 per-GPU work is fixed as N grows. Rank 0 prints one JSON line.
+
+A plain run only sets up, warms up, times the steps and prints the result.
+  --dump-outputs DIR  also writes the last timed step's output columns to
+                      DIR/<column>.npy (inputs are deterministic, so two
+                      builds can be compared output for output)
+  --full              also runs what is not part of the headline figure:
+                      the post-timing multi-rank result gather
 """
 import argparse
 import json
@@ -38,11 +45,15 @@ def make_clip(n, h=H, w=W):
     yy, xx = np.mgrid[0:h, 0:w]
     rng = np.random.RandomState(0)
     texture = rng.randint(0, 32, size=(h, w, 3)).astype(np.int32)
-    frames = np.zeros((n, h, w, 3), np.uint8)
+    # frame i = (base + i * [2, 1, 3]) mod 256 per channel: reduce the
+    # frame-independent part once and let uint8 addition do the wrap
+    base = (np.stack([xx, yy, xx + yy], axis=-1) + texture) % 256
+    base = base.astype(np.uint8).reshape(h, w * 3)
+    step = np.array([2, 1, 3])
+    frames = np.empty((n, h, w, 3), np.uint8)
     for i in range(n):
-        frames[i, :, :, 0] = (xx + i * 2 + texture[:, :, 0]) % 256
-        frames[i, :, :, 1] = (yy + i + texture[:, :, 1]) % 256
-        frames[i, :, :, 2] = (xx + yy + i * 3 + texture[:, :, 2]) % 256
+        shift = np.tile((i * step % 256).astype(np.uint8), w)
+        np.add(base, shift, out=frames[i].reshape(h, w * 3))
     return frames
 
 
@@ -71,6 +82,36 @@ def build_pipeline(sc, sp, video, pipeline, device, out_name):
     return sc.io.Output(cols, [out])
 
 
+DUMP_MAX_BYTES = 64 << 20
+# element type of each saved Bytes column (rows are raw little-endian
+# arrays); integer columns are written as float64, which holds them exactly
+COLUMN_DTYPES = {"histogram": np.uint32}
+
+
+def dump_outputs(sc, sp, table, out_dir):
+    """Write every column of output table `table` — the rows a caller of
+    the timed path loads back — as out_dir/<column>.npy, [rows, elems] in
+    float32 (float columns) or float64 (integer columns). Columns that
+    would push the dump past DUMP_MAX_BYTES keep a fixed seeded subset of
+    rows (ascending row order)."""
+    os.makedirs(out_dir, exist_ok=True)
+    columns = [c[0] for c in sc.table_info(table)["columns"]]
+    budget = DUMP_MAX_BYTES // max(1, len(columns))
+    for col in columns:
+        src = COLUMN_DTYPES.get(col, np.float32)
+        dst = np.float32 if src == np.float32 else np.float64
+        rows = np.stack([np.frombuffer(b, dtype=src) for b in
+                         sp.NamedStream(sc, table, column=col).load()])
+        row_bytes = rows.shape[1] * np.dtype(dst).itemsize
+        keep = max(1, budget // max(1, row_bytes))
+        if keep < len(rows):
+            pick = np.random.RandomState(0).choice(len(rows), keep,
+                                                   replace=False)
+            rows = rows[np.sort(pick)]
+        np.save(os.path.join(out_dir, f"{col}.npy"), rows.astype(dst))
+        log(f"dumped {col}: {rows.shape} -> {out_dir}/{col}.npy")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -79,6 +120,12 @@ def main():
     ap.add_argument("--pipeline", default="full",
                     choices=["hist", "resnet", "full", "flow", "pose"])
     ap.add_argument("--frames-per-step", type=int, default=None)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output columns to "
+                         "DIR/<column>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks that are not part of the "
+                         "headline figure (multi-rank result gather)")
     args = ap.parse_args()
 
     import torch
@@ -180,6 +227,9 @@ def main():
         sc.profile().write_trace(trace_path)
         log(f"[prof] chrome trace -> {trace_path}")
     elapsed = parallel.allreduce_max_time(elapsed, dist_device)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(sc, sp, f"bench_out_s{args.steps-1}",
+                     args.dump_outputs)
 
     total_frames = args.steps * n_frames * world
     fps = total_frames / elapsed
@@ -218,7 +268,7 @@ def main():
         }
         print(json.dumps(result), flush=True)
 
-    if distributed:
+    if distributed and args.full:
         # Post-timing RCCL gather over xGMI: each rank ships the first
         # result rows of its last step's output column to rank 0 (the
         # reference round-trips results through shared storage instead).
@@ -234,6 +284,7 @@ def main():
                     f"{' (RCCL/xGMI)' if dist.get_backend() == 'nccl' else ''}")
         except Exception as e:  # pragma: no cover
             log(f"[rank {rank}] post-bench gather failed: {e}")
+    if distributed:
         dist.destroy_process_group()
     shutil.rmtree(tmp, ignore_errors=True)
 

@@ -62,6 +62,9 @@ assert out == b"weights-payload"
 t = parallel.allreduce_max_time(1.0 + rank, device)
 assert t == 2.0
 print(f"rank {rank} OK", flush=True)
+# orderly shutdown: exiting with the group alive races gloo's background
+# threads against interpreter teardown (std::terminate under load)
+torch.distributed.destroy_process_group()
 """
 
 
@@ -113,7 +116,7 @@ def test_bench_cpu_world2(tmp_path):
         procs.append(subprocess.Popen(
             [sys.executable, os.path.join(REPO, "bench.py"), "--pipeline",
              "hist", "--steps", "1", "--warmup", "0", "--frames-per-step",
-             "8"],
+             "8", "--full"],
             env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE))
     for p in procs:
         out, err = p.communicate(timeout=300)
@@ -124,6 +127,8 @@ def test_bench_cpu_world2(tmp_path):
     assert result["n_gpus"] == 2
     assert result["config"]["parallelism"] == "frame-shard dp2"
     assert result["value"] > 0
+    # --full: the post-timing result gather ran over the collective plane
+    assert "gathered 8 result rows" in outs[0][2], outs[0][2][-2000:]
     # only rank 0 prints the result line (gloo chatter may appear)
     assert not any(ln.startswith("{") for ln in outs[1][1].splitlines())
 
@@ -186,6 +191,7 @@ if rank == 0:
         expect.extend([bytes([r]) * (r * 17)] * r)
     assert got == expect, (len(got), len(expect))
 print(f"rank {rank} OK8", flush=True)
+torch.distributed.destroy_process_group()
 """
 
 

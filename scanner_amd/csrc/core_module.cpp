@@ -85,6 +85,127 @@ py::list profilers_to_py(const std::vector<std::unique_ptr<Profiler>>& profs) {
   return out;
 }
 
+// ---- helpers for the kernel test entry points ----
+
+using FArr = py::array_t<float, py::array::c_style | py::array::forcecast>;
+const DeviceHandle kTestDev{DeviceType::GPU, 0};
+
+// Device buffer that frees itself (also when a check throws mid-binding).
+struct DevBuf {
+  u8* p = nullptr;
+  size_t bytes = 0;
+  explicit DevBuf(size_t n) : bytes(n) {
+    if (n) p = new_buffer(kTestDev, n);
+  }
+  DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; }
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    std::swap(p, o.p);
+    std::swap(bytes, o.bytes);
+    return *this;
+  }
+  ~DevBuf() {
+    if (p) delete_buffer(kTestDev, p);
+  }
+  void poison(void* stream) {
+    if (!p) return;
+    hipError_t e = hipMemsetAsync(p, 0xFF, bytes, (hipStream_t)stream);
+    SCA_CHECK(e == hipSuccess, "test buffer memset failed");
+  }
+};
+
+std::vector<u16> host_to_bf16(const float* p, size_t n) {
+  std::vector<u16> v(n);
+  for (size_t i = 0; i < n; ++i) {
+    u32 bits;
+    std::memcpy(&bits, &p[i], 4);
+    bits += 0x7fff + ((bits >> 16) & 1);  // round to nearest even
+    v[i] = (u16)(bits >> 16);
+  }
+  return v;
+}
+
+DevBuf upload_bf16(const float* p, size_t n) {
+  auto h = host_to_bf16(p, n);
+  DevBuf d(n * 2);
+  if (n) memcpy_buffer(d.p, kTestDev, (u8*)h.data(), CPU_DEVICE, n * 2);
+  return d;
+}
+
+DevBuf upload_f32(const float* p, size_t n) {
+  DevBuf d(n * 4);
+  if (n) memcpy_buffer(d.p, kTestDev, (const u8*)p, CPU_DEVICE, n * 4);
+  return d;
+}
+
+void bf16_to_host(const DevBuf& d, float* out) {
+  size_t n = d.bytes / 2;
+  std::vector<u16> h(n);
+  memcpy_buffer((u8*)h.data(), CPU_DEVICE, d.p, kTestDev, n * 2);
+  for (size_t i = 0; i < n; ++i) {
+    u32 bits = (u32)h[i] << 16;
+    std::memcpy(&out[i], &bits, 4);
+  }
+}
+
+py::array_t<float> download_bf16(const DevBuf& d,
+                                 std::vector<py::ssize_t> shape) {
+  py::array_t<float> out(shape);
+  SCA_CHECK((size_t)out.size() * 2 == d.bytes, "download shape mismatch");
+  bf16_to_host(d, out.mutable_data());
+  return out;
+}
+
+// Optional per-column scale/bias (f32 [N]) and residual ([M][N], rounded
+// to bf16) of the fused GEMM epilogue.
+struct EpilogueBufs {
+  DevBuf scale{0}, bias{0}, residual{0};
+  EpilogueBufs(const py::object& sc, const py::object& bi,
+               const py::object& res, int M, int N) {
+    if (!sc.is_none()) {
+      FArr a = sc.cast<FArr>();
+      SCA_CHECK(a.size() == N, "scale must be [N]");
+      scale = upload_f32(a.data(), N);
+    }
+    if (!bi.is_none()) {
+      FArr a = bi.cast<FArr>();
+      SCA_CHECK(a.size() == N, "bias must be [N]");
+      bias = upload_f32(a.data(), N);
+    }
+    if (!res.is_none()) {
+      FArr a = res.cast<FArr>();
+      SCA_CHECK(a.size() == (py::ssize_t)M * N, "residual must be [M][N]");
+      residual = upload_bf16(a.data(), (size_t)M * N);
+    }
+  }
+  void apply(GemmArgs& g) const {
+    g.scale = (const float*)scale.p;
+    g.bias = (const float*)bias.p;
+    g.residual = residual.p;
+  }
+};
+
+// Launch `repeat` times into dC (re-poisoned before each launch) and
+// return [M][N], or [repeat][M][N] when repeat > 1.
+template <typename F>
+py::array_t<float> run_repeated(int repeat, DevBuf& dC, int M, int N,
+                                F&& launch) {
+  std::vector<py::ssize_t> shape;
+  if (repeat > 1) shape.push_back(repeat);
+  shape.push_back(M);
+  shape.push_back(N);
+  py::array_t<float> out(shape);
+  void* st = per_thread_hip_stream();
+  for (int i = 0; i < repeat; ++i) {
+    dC.poison(st);
+    launch(st);
+    sync_per_thread_stream();
+    bf16_to_host(dC, out.mutable_data() + (size_t)i * M * N);
+  }
+  return out;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_core, m) {
@@ -171,56 +292,267 @@ PYBIND11_MODULE(_core, m) {
     return ms / iters;
   });
 
-  // Raw MFMA GEMM entry for numerics tests: f32 inputs are rounded to
-  // bf16 on the host, C = A @ B_nk^T computed on GPU 0.
-  m.def("gemm_bf16_test",
-        [](py::array_t<float, py::array::c_style | py::array::forcecast> A,
-           py::array_t<float, py::array::c_style | py::array::forcecast> Bnk,
-           bool relu) {
-          SCA_CHECK(have_gpu(), "gemm_bf16_test needs a GPU");
-          int M = (int)A.shape(0), K = (int)A.shape(1);
-          int N = (int)Bnk.shape(0);
-          SCA_CHECK((int)Bnk.shape(1) == K, "K mismatch");
-          DeviceHandle dev{DeviceType::GPU, 0};
-          auto to_bf16 = [](const float* p, size_t n) {
-            std::vector<u16> v(n);
-            for (size_t i = 0; i < n; ++i) {
-              u32 bits;
-              std::memcpy(&bits, &p[i], 4);
-              bits += 0x7fff + ((bits >> 16) & 1);
-              v[i] = (u16)(bits >> 16);
-            }
-            return v;
-          };
-          auto ah = to_bf16(A.data(), (size_t)M * K);
-          auto bh = to_bf16(Bnk.data(), (size_t)N * K);
-          u8* dA = new_buffer(dev, ah.size() * 2);
-          u8* dB = new_buffer(dev, bh.size() * 2);
-          u8* dC = new_buffer(dev, (size_t)M * N * 2);
-          memcpy_buffer(dA, dev, (u8*)ah.data(), CPU_DEVICE, ah.size() * 2);
-          memcpy_buffer(dB, dev, (u8*)bh.data(), CPU_DEVICE, bh.size() * 2);
-          GemmArgs g;
-          g.A = dA;
-          g.B = dB;
-          g.C = dC;
-          g.M = M;
-          g.N = N;
-          g.K = K;
-          g.relu = relu;
-          gemm_bf16(g, per_thread_hip_stream());
-          sync_per_thread_stream();
-          std::vector<u16> ch((size_t)M * N);
-          memcpy_buffer((u8*)ch.data(), CPU_DEVICE, dC, dev, ch.size() * 2);
-          delete_buffer(dev, dA);
-          delete_buffer(dev, dB);
-          delete_buffer(dev, dC);
-          py::array_t<float> out({M, N});
-          float* op = out.mutable_data();
-          for (size_t i = 0; i < ch.size(); ++i) {
-            u32 bits = (u32)ch[i] << 16;
-            std::memcpy(&op[i], &bits, 4);
+  // ---- kernel test entry points (tests/test_dnn_kernels_gpu.py) ----
+  // Common shape: host f32 in, rounded to bf16 on the host, run on GPU 0,
+  // bf16 out returned as f32. Each call allocates, runs and frees its own
+  // buffers; outputs are pre-filled with 0xFF bytes (bf16 NaN) so an
+  // element the kernel never wrote cannot pass a comparison.
+
+  // The dispatch plan for a GEMM/conv shape; pure host code, no GPU needed.
+  m.def(
+      "gemm_plan",
+      [](int M, int N, int K, size_t scratch_bytes, bool is_conv) {
+        GemmPlan p = gemm_plan(M, N, K, scratch_bytes, is_conv);
+        const char* names[] = {"smallk", "splitk", "tile128", "tile64"};
+        py::dict d;
+        d["kernel"] = names[(int)p.kernel];
+        d["splits"] = p.splits;
+        d["ksteps_per_split"] = p.ksteps_per_split;
+        d["tiles_per_wg"] = p.tiles_per_wg;
+        d["grid"] = p.grid;
+        d["swizzle"] = p.swizzle;
+        d["atomic"] = p.atomic;
+        d["fused"] = p.fused;
+        return d;
+      },
+      py::arg("M"), py::arg("N"), py::arg("K"),
+      py::arg("scratch_bytes") = 0, py::arg("is_conv") = false);
+
+  // C = act((A @ B_nk^T) * scale + bias + residual). repeat > 1 launches
+  // that many times on the same scratch and returns [repeat][M][N].
+  m.def(
+      "gemm_bf16_test",
+      [](FArr A, FArr Bnk, bool relu, py::object scale, py::object bias,
+         py::object residual, size_t splitk_scratch_bytes, int repeat) {
+        SCA_CHECK(have_gpu(), "gemm_bf16_test needs a GPU");
+        SCA_CHECK(A.ndim() == 2 && Bnk.ndim() == 2, "A, B must be 2-D");
+        int M = (int)A.shape(0), K = (int)A.shape(1);
+        int N = (int)Bnk.shape(0);
+        SCA_CHECK((int)Bnk.shape(1) == K, "K mismatch");
+        SCA_CHECK(M > 0 && repeat >= 1, "need M > 0 and repeat >= 1");
+        DevBuf dA = upload_bf16(A.data(), (size_t)M * K);
+        DevBuf dB = upload_bf16(Bnk.data(), (size_t)N * K);
+        DevBuf dC((size_t)M * N * 2);
+        EpilogueBufs ep(scale, bias, residual, M, N);
+        DevBuf dS(splitk_scratch_bytes);
+        splitk_scratch_init(dS.p, splitk_scratch_bytes, nullptr);
+        GemmArgs g;
+        g.A = dA.p;
+        g.B = dB.p;
+        g.C = dC.p;
+        g.M = M;
+        g.N = N;
+        g.K = K;
+        g.relu = relu;
+        ep.apply(g);
+        g.splitk_scratch = dS.p;
+        g.splitk_scratch_bytes = splitk_scratch_bytes;
+        return run_repeated(repeat, dC, M, N, [&](void* s) {
+          gemm_bf16(g, s);
+        });
+      },
+      py::arg("A"), py::arg("B_nk"), py::arg("relu") = false, py::kw_only(),
+      py::arg("scale") = py::none(), py::arg("bias") = py::none(),
+      py::arg("residual") = py::none(),
+      py::arg("splitk_scratch_bytes") = 0, py::arg("repeat") = 1);
+
+  // Convolution of an NHWC input with weights [N][kp] laid out
+  // k = (dr*s+ds)*c + cj, kp = r*s*c padded to x64. implicit=True runs the
+  // implicit-GEMM path, implicit=False im2col_bf16 + gemm_bf16. Returns
+  // (out [M][N] or [repeat][M][N], im2col matrix [M][kp]); the im2col
+  // kernel runs in both modes so its matrix is always returned.
+  m.def(
+      "conv_bf16_test",
+      [](FArr x, FArr w_nk, int r, int s, int stride, int pad,
+         py::object scale, py::object bias, py::object residual, bool relu,
+         size_t splitk_scratch_bytes, bool implicit, int repeat) {
+        SCA_CHECK(have_gpu(), "conv_bf16_test needs a GPU");
+        SCA_CHECK(x.ndim() == 4 && w_nk.ndim() == 2, "x NHWC, w [N][kp]");
+        SCA_CHECK(r > 0 && s > 0 && stride > 0 && pad >= 0 && repeat >= 1,
+                  "bad conv geometry");
+        ConvDesc d;
+        d.n = (int)x.shape(0);
+        d.h = (int)x.shape(1);
+        d.w = (int)x.shape(2);
+        d.c = (int)x.shape(3);
+        d.r = r;
+        d.s = s;
+        d.stride = stride;
+        d.pad = pad;
+        SCA_CHECK(d.h + 2 * pad >= r && d.w + 2 * pad >= s,
+                  "filter larger than padded input");
+        d.oh = (d.h + 2 * pad - r) / stride + 1;
+        d.ow = (d.w + 2 * pad - s) / stride + 1;
+        int N = (int)w_nk.shape(0), kp = (int)w_nk.shape(1);
+        int M = d.n * d.oh * d.ow;
+        SCA_CHECK(M > 0 && kp >= r * s * d.c && kp % 64 == 0,
+                  "kp must be r*s*c padded to x64");
+        DevBuf dX = upload_bf16(x.data(), (size_t)x.size());
+        DevBuf dW = upload_bf16(w_nk.data(), (size_t)N * kp);
+        DevBuf dC((size_t)M * N * 2);
+        DevBuf dCols((size_t)M * kp * 2);
+        EpilogueBufs ep(scale, bias, residual, M, N);
+        DevBuf dS(splitk_scratch_bytes);
+        splitk_scratch_init(dS.p, splitk_scratch_bytes, nullptr);
+        void* st = per_thread_hip_stream();
+        dCols.poison(st);
+        im2col_bf16(dX.p, d.n, d.h, d.w, d.c, r, s, stride, pad, dCols.p,
+                    d.oh, d.ow, kp, st);
+        GemmArgs g;
+        g.A = implicit ? dX.p : dCols.p;
+        g.B = dW.p;
+        g.C = dC.p;
+        g.M = M;
+        g.N = N;
+        g.K = kp;
+        g.relu = relu;
+        ep.apply(g);
+        g.splitk_scratch = dS.p;
+        g.splitk_scratch_bytes = splitk_scratch_bytes;
+        py::array_t<float> out = run_repeated(repeat, dC, M, N, [&](void* s2) {
+          if (implicit)
+            conv_gemm_bf16(g, d, s2);
+          else
+            gemm_bf16(g, s2);
+        });
+        return py::make_tuple(out, download_bf16(dCols, {M, kp}));
+      },
+      py::arg("x_nhwc"), py::arg("w_nk"), py::arg("r"), py::arg("s"),
+      py::arg("stride"), py::arg("pad"), py::kw_only(),
+      py::arg("scale") = py::none(), py::arg("bias") = py::none(),
+      py::arg("residual") = py::none(), py::arg("relu") = false,
+      py::arg("splitk_scratch_bytes") = 0, py::arg("implicit") = true,
+      py::arg("repeat") = 1);
+
+  m.def("maxpool3x3s2_bf16_test", [](FArr x) {
+    SCA_CHECK(have_gpu(), "maxpool3x3s2_bf16_test needs a GPU");
+    SCA_CHECK(x.ndim() == 4 && x.size() > 0, "x must be NHWC");
+    int n = (int)x.shape(0), h = (int)x.shape(1), w = (int)x.shape(2),
+        c = (int)x.shape(3);
+    int oh = (h - 1) / 2 + 1, ow = (w - 1) / 2 + 1;
+    DevBuf dX = upload_bf16(x.data(), (size_t)x.size());
+    DevBuf dO((size_t)n * oh * ow * c * 2);
+    void* st = per_thread_hip_stream();
+    dO.poison(st);
+    maxpool3x3s2_bf16(dX.p, n, h, w, c, dO.p, oh, ow, st);
+    sync_per_thread_stream();
+    return download_bf16(dO, {n, oh, ow, c});
+  });
+
+  m.def("global_avgpool_bf16_test", [](FArr x) {
+    SCA_CHECK(have_gpu(), "global_avgpool_bf16_test needs a GPU");
+    SCA_CHECK(x.ndim() == 4 && x.size() > 0, "x must be NHWC");
+    int n = (int)x.shape(0), h = (int)x.shape(1), w = (int)x.shape(2),
+        c = (int)x.shape(3);
+    DevBuf dX = upload_bf16(x.data(), (size_t)x.size());
+    DevBuf dO((size_t)n * c * 2);
+    void* st = per_thread_hip_stream();
+    dO.poison(st);
+    global_avgpool_bf16(dX.p, n, h, w, c, dO.p, st);
+    sync_per_thread_stream();
+    return download_bf16(dO, {n, c});
+  });
+
+  // x: [n][stride_cols] -> f32 [n][ncols] (exact cast of the bf16 values)
+  m.def("bf16_rows_to_f32_test", [](FArr x, int ncols) {
+    SCA_CHECK(have_gpu(), "bf16_rows_to_f32_test needs a GPU");
+    SCA_CHECK(x.ndim() == 2 && x.size() > 0, "x must be [n][stride_cols]");
+    int n = (int)x.shape(0), stride_cols = (int)x.shape(1);
+    SCA_CHECK(ncols > 0 && ncols <= stride_cols, "ncols out of range");
+    DevBuf dX = upload_bf16(x.data(), (size_t)x.size());
+    DevBuf dO((size_t)n * ncols * 4);
+    void* st = per_thread_hip_stream();
+    dO.poison(st);
+    bf16_rows_to_f32(dX.p, n, stride_cols, ncols, dO.p, st);
+    sync_per_thread_stream();
+    py::array_t<float> out({n, ncols});
+    memcpy_buffer((u8*)out.mutable_data(), CPU_DEVICE, dO.p, kTestDev,
+                  (size_t)n * ncols * 4);
+    return out;
+  });
+
+  // a/b/c: [npix][stride] with ca/cb/cc valid channels each
+  m.def("concat3_bf16_test", [](FArr a, int ca, FArr b, int cb, FArr c,
+                                int cc, int out_stride) {
+    SCA_CHECK(have_gpu(), "concat3_bf16_test needs a GPU");
+    SCA_CHECK(a.ndim() == 2 && b.ndim() == 2 && c.ndim() == 2,
+              "inputs must be [npix][stride]");
+    int npix = (int)a.shape(0);
+    SCA_CHECK(npix > 0 && b.shape(0) == npix && c.shape(0) == npix,
+              "npix mismatch");
+    SCA_CHECK(ca >= 0 && cb >= 0 && cc >= 0 && ca <= a.shape(1) &&
+                  cb <= b.shape(1) && cc <= c.shape(1) &&
+                  out_stride >= ca + cb + cc,
+              "channel counts out of range");
+    DevBuf dA = upload_bf16(a.data(), (size_t)a.size());
+    DevBuf dB = upload_bf16(b.data(), (size_t)b.size());
+    DevBuf dCc = upload_bf16(c.data(), (size_t)c.size());
+    DevBuf dO((size_t)npix * out_stride * 2);
+    void* st = per_thread_hip_stream();
+    dO.poison(st);
+    concat3_bf16(dA.p, ca, (int)a.shape(1), dB.p, cb, (int)b.shape(1), dCc.p,
+                 cc, (int)c.shape(1), npix, dO.p, out_stride, st);
+    sync_per_thread_stream();
+    return download_bf16(dO, {npix, out_stride});
+  });
+
+  // maps: [n][h][w][c_stride] -> f32 [n][nch][3] = {x, y, peak}
+  m.def("heatmap_argmax_test", [](FArr maps, int nch) {
+    SCA_CHECK(have_gpu(), "heatmap_argmax_test needs a GPU");
+    SCA_CHECK(maps.ndim() == 4 && maps.size() > 0, "maps must be NHWC");
+    int n = (int)maps.shape(0), h = (int)maps.shape(1),
+        w = (int)maps.shape(2), cs = (int)maps.shape(3);
+    SCA_CHECK(nch > 0 && nch <= cs, "nch out of range");
+    DevBuf dX = upload_bf16(maps.data(), (size_t)maps.size());
+    DevBuf dO((size_t)n * nch * 3 * 4);
+    void* st = per_thread_hip_stream();
+    dO.poison(st);
+    heatmap_argmax(dX.p, n, h, w, cs, nch, dO.p, st);
+    sync_per_thread_stream();
+    py::array_t<float> out({n, nch, 3});
+    memcpy_buffer((u8*)out.mutable_data(), CPU_DEVICE, dO.p, kTestDev,
+                  (size_t)n * nch * 3 * 4);
+    return out;
+  });
+
+  // frames: u8 [n][ih][iw][ic]; uploads the frames and the device pointer
+  // array itself. Returns [n][out_hw][out_hw][out_c].
+  m.def("preprocess_frames_bf16_test",
+        [](py::array_t<u8, py::array::c_style | py::array::forcecast> frames,
+           int out_hw, int out_c, FArr mean, FArr stdv) {
+          SCA_CHECK(have_gpu(), "preprocess_frames_bf16_test needs a GPU");
+          SCA_CHECK(frames.ndim() == 4 && frames.size() > 0,
+                    "frames must be [n][h][w][c]");
+          SCA_CHECK(mean.size() == 3 && stdv.size() == 3 && out_hw > 0 &&
+                        out_c >= 3,
+                    "need 3 mean/std values and out_c >= 3");
+          int n = (int)frames.shape(0), ih = (int)frames.shape(1),
+              iw = (int)frames.shape(2), ic = (int)frames.shape(3);
+          size_t fbytes = (size_t)ih * iw * ic;
+          DevBuf dF(fbytes * n);
+          memcpy_buffer(dF.p, kTestDev, frames.data(), CPU_DEVICE,
+                        fbytes * n);
+          std::vector<const u8*> ptrs(n);
+          for (int i = 0; i < n; ++i) ptrs[i] = dF.p + fbytes * i;
+          DevBuf dP(sizeof(u8*) * n);
+          memcpy_buffer(dP.p, kTestDev, (const u8*)ptrs.data(), CPU_DEVICE,
+                        sizeof(u8*) * n);
+          float ms[6];
+          for (int i = 0; i < 3; ++i) {
+            ms[i] = mean.data()[i];
+            ms[3 + i] = stdv.data()[i];
           }
-          return out;
+          DevBuf dM(sizeof(ms));
+          memcpy_buffer(dM.p, kTestDev, (const u8*)ms, CPU_DEVICE,
+                        sizeof(ms));
+          DevBuf dO((size_t)n * out_hw * out_hw * out_c * 2);
+          void* st = per_thread_hip_stream();
+          dO.poison(st);
+          preprocess_frames_bf16(dP.p, n, ih, iw, ic, out_hw, dO.p,
+                                 (const float*)dM.p, (const float*)dM.p + 3,
+                                 st, out_c);
+          sync_per_thread_stream();
+          return download_bf16(dO, {n, out_hw, out_hw, out_c});
         });
 
   m.def("init_memory", [](size_t cpu_pool, size_t gpu_pool,

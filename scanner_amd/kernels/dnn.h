@@ -27,6 +27,27 @@ struct GemmArgs {
 
 void gemm_bf16(const GemmArgs& g, void* stream);
 
+// Every dispatch decision gemm_bf16 / conv_gemm_bf16 make for a shape, as
+// one pure host function: the launch code calls it and launches exactly
+// what it says, so tests can pin the path table without a GPU
+// (tests/test_gemm_plan.py). scratch_bytes = 0 means "no split-K scratch".
+// The SCANNER_SPLITK_* / SCANNER_SMALLK_WGS env knobs are read once per
+// process.
+enum class GemmKernel { SmallK, SplitK, Tile128, Tile64 };
+
+struct GemmPlan {
+  GemmKernel kernel = GemmKernel::Tile64;
+  int splits = 1;            // split-K groups (1 when not split)
+  int ksteps_per_split = 0;  // 64-wide K steps per split (K/64 when not split)
+  int tiles_per_wg = 1;      // small-K: consecutive M-tiles one workgroup walks
+  int grid = 0;              // workgroups of the main kernel
+  bool swizzle = false;      // tile kernels: grid % 8 == 0 XCD remap applies
+  bool atomic = false;       // split-K: SCANNER_SPLITK_ATOMIC accumulation
+  bool fused = false;        // split-K: SCANNER_SPLITK_FUSED in-kernel reduce
+};
+
+GemmPlan gemm_plan(int M, int N, int K, size_t scratch_bytes, bool is_conv);
+
 // Zero the fused-reduce tile-counter region at the TAIL of a split-K
 // scratch buffer. Owners must call this ONCE when they allocate the
 // scratch (the kernel self-restores the counters to zero after each

@@ -308,7 +308,9 @@ __global__ void __launch_bounds__(256)
 
 // Per-(frame, channel) spatial argmax over an NHWC bf16 map with padded
 // channel stride: out[frame][ch] = {x, y, score} f32. One workgroup per
-// (frame, channel); wave64 shuffle reduction.
+// (frame, channel); wave64 shuffle reduction. Ties at the peak resolve to
+// the lowest flat index y*w+x (numpy.argmax order): a thread owns indices
+// t, t+256, ..., so "lower lane / lower wave wins" alone would not be that.
 __global__ void __launch_bounds__(256)
     heatmap_argmax_kernel(const bf16* __restrict__ maps, int h, int w,
                           int c_stride, int nch, float* __restrict__ out) {
@@ -328,7 +330,7 @@ __global__ void __launch_bounds__(256)
   for (int off = 32; off; off >>= 1) {
     float ov = __shfl_down(best, off, 64);
     int oi = __shfl_down(besti, off, 64);
-    if (ov > best) {
+    if (ov > best || (ov == best && oi < besti)) {
       best = ov;
       besti = oi;
     }
@@ -341,7 +343,7 @@ __global__ void __launch_bounds__(256)
   __syncthreads();
   if (threadIdx.x == 0) {
     for (int wv = 1; wv < (int)blockDim.x / 64; ++wv) {
-      if (lbest[wv] > best) {
+      if (lbest[wv] > best || (lbest[wv] == best && lidx[wv] < besti)) {
         best = lbest[wv];
         besti = lidx[wv];
       }

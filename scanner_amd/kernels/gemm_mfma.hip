@@ -707,8 +707,11 @@ __global__ void __launch_bounds__(256)
 
 const bf16* device_zero_chunk();
 
-bool try_splitk(const GemmArgs& g, hipStream_t s,
-                const ConvDesc* dd = nullptr) {
+constexpr size_t kSplitkCtrBytes = 4096;  // tile counters at the scratch tail
+
+// Split-K decision (the launch below follows it verbatim). Returns false
+// when the shape should not split.
+bool plan_splitk(int M, int N, int K, size_t scratch_bytes, GemmPlan& p) {
   constexpr int BM = 128, BN = 128;
   // SCANNER_SPLITK_OFF=1: skip split-K entirely (A/B: with multiple
   // pipeline instances co-running, their kernels may fill the chip
@@ -718,9 +721,9 @@ bool try_splitk(const GemmArgs& g, hipStream_t s,
     return e && e[0] == '1';
   }();
   if (kOff) return false;
-  if (!g.splitk_scratch || g.N % BN != 0 || g.K < 1024) return false;
-  int ntiles_m = (g.M + BM - 1) / BM;
-  int tiles = ntiles_m * (g.N / BN);
+  if (!scratch_bytes || N % BN != 0 || K < 1024) return false;
+  int ntiles_m = (M + BM - 1) / BM;
+  int tiles = ntiles_m * (N / BN);
   if (tiles >= 256) return false;  // already fills the chip
   static const int kMaxSplits = []() {
     const char* e = std::getenv("SCANNER_SPLITK_MAX");
@@ -729,22 +732,20 @@ bool try_splitk(const GemmArgs& g, hipStream_t s,
     // fed by the co-running pipeline instances.
     return e ? std::max(2, atoi(e)) : 6;
   }();
-  int ksteps = g.K / 64;
+  int ksteps = K / 64;
   int want = std::min({kMaxSplits, ksteps / 4, (2048 + tiles - 1) / tiles});
-  size_t per_split = (size_t)g.M * g.N * 4;
+  size_t per_split = (size_t)M * N * 4;
   // The scratch tail holds the fused-reduce tile counters (tiles < 256 so
   // 4 KB is ample); the owner zeroes it once at allocation
   // (splitk_scratch_init) and the kernel self-restores it after each use.
-  constexpr size_t kCtrBytes = 4096;
-  size_t avail = g.splitk_scratch_bytes > kCtrBytes
-                     ? g.splitk_scratch_bytes - kCtrBytes
+  size_t avail = scratch_bytes > kSplitkCtrBytes
+                     ? scratch_bytes - kSplitkCtrBytes
                      : 0;
   int fit = (int)(avail / per_split);
   int splits = std::min(want, fit);
   if (splits < 2) return false;
   int ksteps_per_split = (ksteps + splits - 1) / splits;
   splits = (ksteps + ksteps_per_split - 1) / ksteps_per_split;
-  i64 mn = (i64)g.M * g.N;
   // Atomic accumulation (opt-in, SCANNER_SPLITK_ATOMIC=1): one pre-zeroed
   // f32 [M][N] buffer, no S x M x N reduce read — but f32 atomic-add
   // ORDER is nondeterministic, so results vary at the last bf16 ulp
@@ -758,8 +759,9 @@ bool try_splitk(const GemmArgs& g, hipStream_t s,
   // Fused reduce (opt-in, SCANNER_SPLITK_FUSED=1; default OFF). Measured
   // NEGATIVE on MI355X: flagship 7.6k vs 16.6k f/s, resnet 7.9k vs 18.0k
   // (same box, 3-step A/B, profiles/r02_results.md update 12). Numerics
-  // are correct (27 GPU tests green with it on), but the device-scope
-  // release fence every workgroup needs before bumping its tile counter
+  // are correct (tests/test_dnn_kernels_gpu.py holds it bit-equal to the
+  // default path), but the device-scope release fence every workgroup
+  // needs before bumping its tile counter
   // forces an L2 writeback per WG — on 8 per-XCD L2s that evicts the
   // B-operand and co-running instances' working sets — and the tail
   // reduce runs with one 256-thread WG per tile vs the standalone
@@ -769,11 +771,28 @@ bool try_splitk(const GemmArgs& g, hipStream_t s,
     const char* e = std::getenv("SCANNER_SPLITK_FUSED");
     return e && e[0] == '1';
   }();
-  bool fused = kFused && !kAtomic;
+  p.kernel = GemmKernel::SplitK;
+  p.splits = splits;
+  p.ksteps_per_split = ksteps_per_split;
+  p.grid = tiles * splits;
+  p.atomic = kAtomic;
+  p.fused = kFused && !kAtomic;
+  return true;
+}
+
+void launch_splitk(const GemmArgs& g, hipStream_t s, const GemmPlan& p,
+                   const ConvDesc* dd = nullptr) {
+  constexpr int BM = 128, BN = 128;
+  const int splits = p.splits;
+  const int ksteps_per_split = p.ksteps_per_split;
+  const int grid_main = p.grid;
+  const bool kAtomic = p.atomic;
+  const bool fused = p.fused;
+  i64 mn = (i64)g.M * g.N;
   SplitkEp ep{};
   if (fused) {
     ep.counters = reinterpret_cast<unsigned int*>(
-        (u8*)g.splitk_scratch + g.splitk_scratch_bytes - kCtrBytes);
+        (u8*)g.splitk_scratch + g.splitk_scratch_bytes - kSplitkCtrBytes);
     ep.splits = splits;
     ep.scale = g.scale;
     ep.bias = g.bias;
@@ -790,26 +809,26 @@ bool try_splitk(const GemmArgs& g, hipStream_t s,
     }
     if (dd) {
       gemm_bf16_splitk_kernel<BM, BN, 2, 2, true, true>
-          <<<tiles * splits, 256, 0, s>>>(
+          <<<grid_main, 256, 0, s>>>(
               (const bf16*)g.A, (const bf16*)g.B, g.M, g.N, g.K,
               ksteps_per_split, (float*)g.splitk_scratch, *dd,
               device_zero_chunk(), SplitkEp{});
     } else {
       gemm_bf16_splitk_kernel<BM, BN, 2, 2, false, true>
-          <<<tiles * splits, 256, 0, s>>>(
+          <<<grid_main, 256, 0, s>>>(
               (const bf16*)g.A, (const bf16*)g.B, g.M, g.N, g.K,
               ksteps_per_split, (float*)g.splitk_scratch, ConvDesc{},
               nullptr, SplitkEp{});
     }
   } else if (dd) {
     gemm_bf16_splitk_kernel<BM, BN, 2, 2, true, false>
-        <<<tiles * splits, 256, 0, s>>>(
+        <<<grid_main, 256, 0, s>>>(
             (const bf16*)g.A, (const bf16*)g.B, g.M, g.N, g.K,
             ksteps_per_split, (float*)g.splitk_scratch, *dd,
             device_zero_chunk(), ep);
   } else {
     gemm_bf16_splitk_kernel<BM, BN, 2, 2, false, false>
-        <<<tiles * splits, 256, 0, s>>>(
+        <<<grid_main, 256, 0, s>>>(
             (const bf16*)g.A, (const bf16*)g.B, g.M, g.N, g.K,
             ksteps_per_split, (float*)g.splitk_scratch, ConvDesc{}, nullptr,
             ep);
@@ -819,7 +838,7 @@ bool try_splitk(const GemmArgs& g, hipStream_t s,
     throw ScannerError(std::string("splitk launch failed: ") +
                        hipGetErrorString(e));
   }
-  if (fused) return true;  // epilogue ran in-kernel; no reduce launch
+  if (fused) return;  // epilogue ran in-kernel; no reduce launch
   // 4x more threads than quads: the extra waves are pure memory-level
   // parallelism for this latency-bound pass (measured 18.2 us avg vs a
   // ~1.3 us bandwidth bound)
@@ -850,13 +869,12 @@ bool try_splitk(const GemmArgs& g, hipStream_t s,
     throw ScannerError(std::string("splitk reduce launch failed: ") +
                        hipGetErrorString(e));
   }
-  return true;
 }
 
-void launch_smallk(const GemmArgs& g, hipStream_t s) {
+void plan_smallk(int M, int N, GemmPlan& p) {
   constexpr int BM = 128, BN = 128;
-  int ntiles_m = (g.M + BM - 1) / BM;
-  int ntiles_n = (g.N + BN - 1) / BN;
+  int ntiles_m = (M + BM - 1) / BM;
+  int ntiles_n = (N + BN - 1) / BN;
   // Enough strips to fill the chip (>=2048 workgroups when the shape
   // allows), each walking a run of consecutive M-tiles.
   static const int target_wgs = []() {
@@ -866,7 +884,15 @@ void launch_smallk(const GemmArgs& g, hipStream_t s) {
   int strips = std::max(1, std::min(ntiles_m, target_wgs / ntiles_n));
   int tiles_per_wg = (ntiles_m + strips - 1) / strips;
   strips = (ntiles_m + tiles_per_wg - 1) / tiles_per_wg;
-  int grid = strips * ntiles_n;
+  p.kernel = GemmKernel::SmallK;
+  p.tiles_per_wg = tiles_per_wg;
+  p.grid = strips * ntiles_n;
+}
+
+void launch_smallk(const GemmArgs& g, hipStream_t s, const GemmPlan& p) {
+  constexpr int BM = 128, BN = 128;
+  const int grid = p.grid;
+  const int tiles_per_wg = p.tiles_per_wg;
   auto disp = [&](auto relu, auto res) {
     gemm_bf16_smallk_kernel<BM, BN, 2, 2, decltype(relu)::value,
                             decltype(res)::value><<<grid, 256, 0, s>>>(
@@ -889,8 +915,8 @@ void launch_smallk(const GemmArgs& g, hipStream_t s) {
 }
 
 template <int BM, int BN, int WM, int WN>
-void launch_variant(const GemmArgs& g, hipStream_t s) {
-  int grid = ((g.M + BM - 1) / BM) * (g.N / BN);
+void launch_variant(const GemmArgs& g, hipStream_t s, const GemmPlan& p) {
+  const int grid = p.grid;
   auto disp = [&](auto relu, auto res) {
     gemm_bf16_kernel<BM, BN, WM, WN, decltype(relu)::value,
                      decltype(res)::value, false><<<grid, 256, 0, s>>>(
@@ -934,8 +960,8 @@ const bf16* device_zero_chunk() {
 
 template <int BM, int BN, int WM, int WN>
 void launch_conv_variant(const GemmArgs& g, const ConvDesc& d,
-                         hipStream_t s) {
-  int grid = ((g.M + BM - 1) / BM) * (g.N / BN);
+                         hipStream_t s, const GemmPlan& p) {
+  const int grid = p.grid;
   const bf16* zero = device_zero_chunk();
   auto disp = [&](auto relu, auto res) {
     gemm_bf16_kernel<BM, BN, WM, WN, decltype(relu)::value,
@@ -960,18 +986,43 @@ void launch_conv_variant(const GemmArgs& g, const ConvDesc& d,
 
 }  // namespace
 
+GemmPlan gemm_plan(int M, int N, int K, size_t scratch_bytes, bool is_conv) {
+  SCA_CHECK(K % 64 == 0 && N % 64 == 0, "gemm K/N must be x64");
+  GemmPlan p;
+  p.ksteps_per_split = K / 64;
+  if (!is_conv && K == 64 && N % 128 == 0 && M >= 1024) {
+    plan_smallk(M, N, p);
+    return p;
+  }
+  if (plan_splitk(M, N, K, scratch_bytes, p)) return p;
+  // the implicit-conv path has no M > 64 condition
+  bool big = N % 128 == 0 && (is_conv || M > 64);
+  int bt = big ? 128 : 64;
+  p.kernel = big ? GemmKernel::Tile128 : GemmKernel::Tile64;
+  p.grid = ((M + bt - 1) / bt) * (N / bt);
+  p.swizzle = p.grid % 8 == 0;
+  return p;
+}
+
 void conv_gemm_bf16(const GemmArgs& g, const ConvDesc& d, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   SCA_CHECK(g.K % 64 == 0 && g.N % 64 == 0, "conv gemm K/N must be x64");
   SCA_CHECK(d.c % 8 == 0, "implicit conv needs c % 8 == 0");
   SCA_CHECK(g.M == d.n * d.oh * d.ow, "conv gemm M mismatch");
-  if (try_splitk(g, s, &d)) {
-    return;
-  }
-  if (g.N % 128 == 0) {
-    launch_conv_variant<128, 128, 2, 2>(g, d, s);
-  } else {
-    launch_conv_variant<64, 64, 2, 2>(g, d, s);
+  GemmPlan p = gemm_plan(g.M, g.N, g.K,
+                         g.splitk_scratch ? g.splitk_scratch_bytes : 0, true);
+  switch (p.kernel) {
+    case GemmKernel::SplitK:
+      launch_splitk(g, s, p, &d);
+      break;
+    case GemmKernel::Tile128:
+      launch_conv_variant<128, 128, 2, 2>(g, d, s, p);
+      break;
+    case GemmKernel::Tile64:
+      launch_conv_variant<64, 64, 2, 2>(g, d, s, p);
+      break;
+    case GemmKernel::SmallK:
+      SCA_CHECK(false, "conv gemm has no small-K path");
   }
 }
 
@@ -988,14 +1039,21 @@ void gemm_bf16(const GemmArgs& g, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   SCA_CHECK(g.K % 64 == 0, "gemm K must be a multiple of 64");
   SCA_CHECK(g.N % 64 == 0, "gemm N must be a multiple of 64");
-  if (g.K == 64 && g.N % 128 == 0 && g.M >= 1024) {
-    launch_smallk(g, s);
-  } else if (try_splitk(g, s)) {
-    // handled
-  } else if (g.N % 128 == 0 && g.M > 64) {
-    launch_variant<128, 128, 2, 2>(g, s);
-  } else {
-    launch_variant<64, 64, 2, 2>(g, s);
+  GemmPlan p = gemm_plan(g.M, g.N, g.K,
+                         g.splitk_scratch ? g.splitk_scratch_bytes : 0, false);
+  switch (p.kernel) {
+    case GemmKernel::SmallK:
+      launch_smallk(g, s, p);
+      break;
+    case GemmKernel::SplitK:
+      launch_splitk(g, s, p);
+      break;
+    case GemmKernel::Tile128:
+      launch_variant<128, 128, 2, 2>(g, s, p);
+      break;
+    case GemmKernel::Tile64:
+      launch_variant<64, 64, 2, 2>(g, s, p);
+      break;
   }
 }
 

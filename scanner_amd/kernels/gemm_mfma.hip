@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <map>
 #include <mutex>
+#include <type_traits>
 
 #include "../csrc/memory.h"
 #include "dnn.h"
@@ -30,6 +31,64 @@ __device__ inline float bf16_to_f32(bf16 v) { return (float)v; }
 
 __device__ inline bf16 f32_to_bf16(float v) { return (bf16)v; }
 
+__device__ inline void glds16(const bf16* src, bf16* lds_dst) {
+  __builtin_amdgcn_global_load_lds(
+      (const __attribute__((address_space(1))) uint32_t*)src,
+      (__attribute__((address_space(3))) uint32_t*)lds_dst, 16, 0, 0);
+}
+
+// The wave's FN per-column scale and bias values (folded BN), one register
+// each: column n0 + wcol*COLS + j*16 + (lane & 15) = col0 + j*16. Loaded
+// once per workgroup, unconditionally behind ONE workgroup-uniform null
+// test per pointer. (A `scale ? scale[col] : 1.f` per fragment makes hipcc
+// branch around each load and wait vmcnt(0) right after it: 2*FM*FN
+// dependent L2 round trips per workgroup.) Callers issue this before their
+// first stage(), so the K loop's first vmcnt(0) retires the loads for free.
+template <int FN>
+__device__ inline void load_scale_bias(float (&sc)[FN], float (&bi)[FN],
+                                       const float* __restrict__ scale,
+                                       const float* __restrict__ bias,
+                                       int col0) {
+  if (scale) {
+#pragma unroll
+    for (int j = 0; j < FN; ++j) sc[j] = scale[col0 + j * 16];
+  } else {
+#pragma unroll
+    for (int j = 0; j < FN; ++j) sc[j] = 1.f;
+  }
+  if (bias) {
+#pragma unroll
+    for (int j = 0; j < FN; ++j) bi[j] = bias[col0 + j * 16];
+  } else {
+#pragma unroll
+    for (int j = 0; j < FN; ++j) bi[j] = 0.f;
+  }
+}
+
+// All of a wave's residual reads for one output tile, issued back to back:
+// FM 16-row blocks x CHUNK/8 16-byte loads per lane, in the layout
+// epilogue_store consumes (lane -> row lane>>2, CHUNK columns from chunk
+// lane&3). Rows past M are clamped to M-1 (never stored), which keeps the
+// loads free of branches.
+template <int FM, int FN>
+__device__ inline void load_residual(bf16x8 (&res)[FM][FN / 2],
+                                     const bf16* __restrict__ residual,
+                                     int M, int N, int m0, int n0, int wrow,
+                                     int wcol, int lane) {
+  constexpr int COLS = FN * 16;
+  constexpr int CHUNK = COLS / 4;
+  int colbase = n0 + wcol * COLS + (lane & 3) * CHUNK;
+#pragma unroll
+  for (int i = 0; i < FM; ++i) {
+    int row = m0 + wrow * (FM * 16) + i * 16 + (lane >> 2);
+    row = row < M ? row : M - 1;
+    const bf16* src = residual + (size_t)row * N + colbase;
+#pragma unroll
+    for (int c = 0; c < CHUNK / 8; ++c)
+      res[i][c] = *reinterpret_cast<const bf16x8*>(src + c * 8);
+  }
+}
+
 // Coalesced epilogue: the MFMA fragment layout leaves each lane holding
 // 4 rows x 1 col, so direct stores are 2-byte scattered (measured 1.4 TB/s
 // on store-bound shapes — 1/6 of HBM). Transpose each 16-row block through
@@ -37,15 +96,17 @@ __device__ inline bf16 f32_to_bf16(float v) { return (bf16)v; }
 // 16 consecutive cols per lane), then store 32 contiguous bytes per lane —
 // full 64-byte-per-4-lane coalescing. Scratch is per-wave, so only
 // intra-wave lgkmcnt ordering is needed: no block barrier, which keeps the
-// small-K kernel's cross-tile A prefetch in flight.
+// small-K kernel's cross-tile A prefetch in flight. Scale, bias and the
+// residual arrive in registers (load_scale_bias / load_residual): no global
+// load is issued in here.
 template <int FM, int FN, bool RELU, bool RESIDUAL>
 __device__ inline void epilogue_store(f32x4 (&acc)[FM][FN], float* scratch,
                                       bf16* __restrict__ C,
-                                      const bf16* __restrict__ residual,
-                                      int M, int N, int m0, int n0, int wrow,
+                                      const bf16x8 (&res)[FM][FN / 2], int M,
+                                      int N, int m0, int n0, int wrow,
                                       int wcol, int lane,
-                                      const float* __restrict__ scale,
-                                      const float* __restrict__ bias) {
+                                      const float (&sc)[FN],
+                                      const float (&bi)[FN]) {
   constexpr int COLS = FN * 16;
   constexpr int STRIDE = COLS + 4;  // keeps 16 B row alignment, breaks banks
 #pragma unroll
@@ -54,13 +115,10 @@ __device__ inline void epilogue_store(f32x4 (&acc)[FM][FN], float* scratch,
 #pragma unroll
     for (int j = 0; j < FN; ++j) {
       int cw = j * 16 + (lane & 15);
-      int col = n0 + wcol * COLS + cw;
-      float sc = scale ? scale[col] : 1.f;
-      float bi = bias ? bias[col] : 0.f;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         scratch[((lane >> 4) * 4 + r) * STRIDE + cw] =
-            acc[i][j][r] * sc + bi;
+            acc[i][j][r] * sc[j] + bi[j];
       }
     }
     asm volatile("s_waitcnt lgkmcnt(0)");  // writes visible to own reads
@@ -76,9 +134,7 @@ __device__ inline void epilogue_store(f32x4 (&acc)[FM][FN], float* scratch,
 #pragma unroll
       for (int k = 0; k < CHUNK; ++k) {
         float v = src[k];
-        if constexpr (RESIDUAL) {
-          v += bf16_to_f32(residual[(size_t)row * N + colbase + k]);
-        }
+        if constexpr (RESIDUAL) v += bf16_to_f32(res[i][k / 8][k % 8]);
         if constexpr (RELU) v = v > 0.f ? v : 0.f;
         out[k] = f32_to_bf16(v);
       }
@@ -92,14 +148,190 @@ __device__ inline void epilogue_store(f32x4 (&acc)[FM][FN], float* scratch,
   }
 }
 
+// LDS staging of one BM x 64 A tile and one BN x 64 B tile per K step, for
+// the tile kernel and the split-K kernel alike. Each wave covers 8 rows x
+// 64 k per LDS-DMA instruction (64 lanes x 16 B = 8 bf16 each): BM/32
+// instructions per wave for A, BN/32 for B. All divisions happen in
+// init(); advance() and issue() do none, and issue() has no branch around
+// a DMA: the zero-or-address choice is a select, so the DMAs of a step go
+// out back to back.
+//
+// IMPLICIT: A is the NHWC activation tensor and the staging gathers im2col
+// rows on the fly (ConvDesc d gives the geometry; zero points at 16+ zero
+// bytes for padding / k-pad lanes). Lane-addressed global_load_lds makes
+// the gather free of any HBM im2col round trip.
+//  - generic (any c % 8 == 0; conv1's c = 8, c = 24): per lane, the
+//    output-pixel part of the gather address is k-independent and
+//    (cell, cj, dr, ds) advance by a constant per step; the former is
+//    precomputed, the latter stepped incrementally.
+//  - FAST (c % 64 == 0, r*s <= 32, K == r*s*c; chosen on the host — every
+//    3x3 and strided 1x1 conv of ResNet-50): a 64-wide step never leaves
+//    one (r, s) cell, so cell/dr/ds and the step's element offset are
+//    workgroup-uniform scalars. Per lane and row only a base pointer (tap
+//    (0,0), may lie outside the image — it is dereferenced only when the
+//    tap's validity bit is set) and a validity word with one bit per tap
+//    are kept. A DMA then costs an add of the uniform offset, a bit test
+//    and a select.
+template <int BM, int BN, bool IMPLICIT, bool FAST>
+struct TileStager {
+  static constexpr int BK = 64;
+  static constexpr int A_INSTRS = BM / 8 / 4;  // per wave
+  static constexpr int B_INSTRS = BN / 8 / 4;
+  static_assert(IMPLICIT || !FAST, "FAST is an implicit-conv mode");
+
+  const bf16* b_src[B_INSTRS];    // at the current k
+  const bf16* a_src[A_INSTRS];    // direct: at the current k; FAST: tap (0,0)
+  uint32_t valid[A_INSTRS];       // FAST: bit (dr*s + ds) = tap inside image
+  i64 rowbase[A_INSTRS];          // generic: nn*h*w*c
+  int hh0[A_INSTRS];              // generic: p*stride - pad
+  int ww0[A_INSTRS];              // generic: q*stride - pad
+  int cell, cj, dr, ds;           // generic: per lane; FAST: uniform
+
+  // k0: first k of the first step (a multiple of 64, workgroup-uniform)
+  __device__ inline void init(const bf16* __restrict__ A,
+                              const bf16* __restrict__ B, int M, int K,
+                              int m0, int n0, int wave, int lane, int k0,
+                              const ConvDesc& d) {
+    const int lrow = lane >> 3;     // 0..7 row within instr block
+    const int lk = (lane & 7) * 8;  // k offset (8 bf16 = 16B)
+#pragma unroll
+    for (int i = 0; i < B_INSTRS; ++i) {
+      int row = (wave * B_INSTRS + i) * 8 + lrow;
+      b_src[i] = B + (size_t)(n0 + row) * K + k0 + lk;
+    }
+#pragma unroll
+    for (int i = 0; i < A_INSTRS; ++i) {
+      int row = (wave * A_INSTRS + i) * 8 + lrow;
+      int grow = m0 + row;
+      if (grow >= M) grow = M - 1;  // clamp: garbage rows masked at store
+      if constexpr (!IMPLICIT) {
+        a_src[i] = A + (size_t)grow * K + k0 + lk;
+      } else {
+        int q = grow % d.ow;
+        int t = grow / d.ow;
+        int p = t % d.oh;
+        int nn = t / d.oh;
+        int h0 = p * d.stride - d.pad;
+        int w0 = q * d.stride - d.pad;
+        if constexpr (FAST) {
+          a_src[i] =
+              A + ((((i64)nn * d.h + h0) * d.w + w0) * d.c + lk);
+          uint32_t cmask = 0;
+          for (int x = 0; x < d.s; ++x)
+            cmask |= (uint32_t)((unsigned)(w0 + x) < (unsigned)d.w) << x;
+          uint32_t v = 0;
+          for (int y = 0; y < d.r; ++y)
+            v |= ((unsigned)(h0 + y) < (unsigned)d.h) ? cmask << (y * d.s)
+                                                     : 0u;
+          valid[i] = v;
+        } else {
+          rowbase[i] = (i64)nn * d.h * d.w * d.c;
+          hh0[i] = h0;
+          ww0[i] = w0;
+        }
+      }
+    }
+    if constexpr (IMPLICIT) {
+      int k = FAST ? k0 : k0 + lk;
+      cell = k / d.c;
+      cj = k - cell * d.c;
+      dr = cell / d.s;
+      ds = cell - dr * d.s;
+    }
+  }
+
+  // step to the next 64 k
+  __device__ inline void advance(const ConvDesc& d) {
+#pragma unroll
+    for (int i = 0; i < B_INSTRS; ++i) b_src[i] += BK;
+    if constexpr (!IMPLICIT) {
+#pragma unroll
+      for (int i = 0; i < A_INSTRS; ++i) a_src[i] += BK;
+    } else {
+      // c >= 8, so the generic wrap loop is short; with FAST (c % 64 == 0)
+      // it runs at most once and on scalars
+      cj += BK;
+      while (cj >= d.c) {
+        cj -= d.c;
+        ++cell;
+        ++ds;
+        if (ds == d.s) {
+          ds = 0;
+          ++dr;
+        }
+      }
+    }
+  }
+
+  // issue the current step's DMAs into the buffer at lds_a
+  // ([BM rows of A][BN rows of B], 64 k each)
+  __device__ inline void issue(bf16* lds_a, int wave,
+                               const bf16* __restrict__ A,
+                               const ConvDesc& d,
+                               const bf16* __restrict__ zero) const {
+    bf16* lds_b = lds_a + BM * BK;
+    i64 step_off = 0;
+    if constexpr (FAST) step_off = ((i64)dr * d.w + ds) * d.c + cj;
+#pragma unroll
+    for (int i = 0; i < A_INSTRS; ++i) {
+      const bf16* src;
+      if constexpr (!IMPLICIT) {
+        src = a_src[i];
+      } else if constexpr (FAST) {
+        src = ((valid[i] >> cell) & 1u) ? a_src[i] + step_off : zero;
+      } else {
+        int hh = hh0[i] + dr;
+        int ww = ww0[i] + ds;
+        bool ok = cell < d.r * d.s && (unsigned)hh < (unsigned)d.h &&
+                  (unsigned)ww < (unsigned)d.w;
+        const bf16* in =
+            A + (rowbase[i] + ((i64)hh * d.w + ww) * d.c + cj);
+        src = ok ? in : zero;
+      }
+      glds16(src, lds_a + (size_t)(wave * A_INSTRS + i) * 8 * BK);
+    }
+#pragma unroll
+    for (int i = 0; i < B_INSTRS; ++i)
+      glds16(b_src[i], lds_b + (size_t)(wave * B_INSTRS + i) * 8 * BK);
+  }
+};
+
+// One 64-wide K step of MFMAs on the staged tile at lds_a.
+template <int BM, int BN, int WM, int WN, int FM, int FN>
+__device__ inline void mfma_step(f32x4 (&acc)[FM][FN], const bf16* lds_a,
+                                 int wrow, int wcol, int lane) {
+  constexpr int BK = 64;
+  const bf16* lds_b = lds_a + BM * BK;
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk) {  // two K=32 chunks per BK
+    int kbase = kk * 32 + (lane >> 4) * 8;
+    bf16x8 afrag[FM], bfrag[FN];
+#pragma unroll
+    for (int i = 0; i < FM; ++i) {
+      int row = wrow * (BM / WM) + i * 16 + (lane & 15);
+      afrag[i] = *reinterpret_cast<const bf16x8*>(
+          lds_a + (size_t)row * BK + kbase);
+    }
+#pragma unroll
+    for (int j = 0; j < FN; ++j) {
+      int col = wcol * (BN / WN) + j * 16 + (lane & 15);
+      bfrag[j] = *reinterpret_cast<const bf16x8*>(
+          lds_b + (size_t)col * BK + kbase);
+    }
+#pragma unroll
+    for (int i = 0; i < FM; ++i)
+#pragma unroll
+      for (int j = 0; j < FN; ++j)
+        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            afrag[i], bfrag[j], acc[i][j], 0, 0, 0);
+  }
+}
+
 // One workgroup = 256 threads = 4 waves in a WM x WN grid; each wave owns
 // a (BM/WM) x (BN/WN) output sub-tile as FM x FN fragments of 16x16.
-// When IMPLICIT, A is the NHWC activation tensor and the A staging
-// gathers im2col rows on the fly (ConvDesc d gives the geometry; zero
-// points at 16+ zero bytes for padding / k-pad lanes). Lane-addressed
-// global_load_lds makes the gather free of any HBM im2col round trip.
+// IMPLICIT / FAST: see TileStager.
 template <int BM, int BN, int WM, int WN, bool RELU, bool RESIDUAL,
-          bool IMPLICIT>
+          bool IMPLICIT, bool FAST>
 __global__ void __launch_bounds__(256, 2)
     gemm_bf16_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B,
                      bf16* __restrict__ C, int M, int N, int K,
@@ -131,158 +363,60 @@ __global__ void __launch_bounds__(256, 2)
   int m0 = (wgid / ntiles_n) * BM;
   int n0 = (wgid % ntiles_n) * BN;
 
+  // epilogue operands first: the K loop's first vmcnt(0) retires them
+  float sc[FN], bi[FN];
+  load_scale_bias<FN>(sc, bi, scale, bias,
+                      n0 + wcol * (FN * 16) + (lane & 15));
+
   f32x4 acc[FM][FN];
 #pragma unroll
   for (int i = 0; i < FM; ++i)
 #pragma unroll
     for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  // Staging: each wave covers 8 rows x 64 k per glds instruction
-  // (64 lanes x 16 B = 8 bf16 each). A tile: BM rows -> BM/8 instrs
-  // over 4 waves; same for B.
-  constexpr int A_INSTRS = BM / 8 / 4;  // per wave
-  constexpr int B_INSTRS = BN / 8 / 4;
-  // Implicit-conv staging geometry: the output-pixel part of each lane's
-  // gather address is k-independent, and (cell, cj, dr, ds) advance by a
-  // constant per BK step — precompute the former, step the latter
-  // incrementally so the hot stage() does ZERO integer divisions (3 divs
-  // per LDS-DMA instruction otherwise; K/64 steps x 4 instrs adds up).
-  const int lrow = lane >> 3;          // 0..7 row within instr block
-  const int lk = (lane & 7) * 8;       // k offset (8 bf16 = 16B)
-  i64 imp_rowbase[IMPLICIT ? A_INSTRS : 1];  // nn*h*w*c + cj later
-  int imp_hh0[IMPLICIT ? A_INSTRS : 1];      // p*stride - pad
-  int imp_ww0[IMPLICIT ? A_INSTRS : 1];      // q*stride - pad
-  int imp_cell = 0, imp_cj = 0, imp_dr = 0, imp_ds = 0;
-  if constexpr (IMPLICIT) {
-#pragma unroll
-    for (int i = 0; i < A_INSTRS; ++i) {
-      int row = (wave * A_INSTRS + i) * 8 + lrow;
-      int grow = m0 + row;
-      if (grow >= M) grow = M - 1;
-      int q = grow % d.ow;
-      int t = grow / d.ow;
-      int p = t % d.oh;
-      int nn = t / d.oh;
-      imp_rowbase[i] = (i64)nn * d.h * d.w * d.c;
-      imp_hh0[i] = p * d.stride - d.pad;
-      imp_ww0[i] = q * d.stride - d.pad;
-    }
-    imp_cell = lk / d.c;
-    imp_cj = lk - imp_cell * d.c;
-    imp_dr = imp_cell / d.s;
-    imp_ds = imp_cell - imp_dr * d.s;
-  }
-  auto imp_advance = [&](int dk) {
-    // advance (cell, cj) by dk k-positions; c >= 8 so the wrap loop is
-    // short and branch-uniform across the wave (same cj for all lanes of
-    // one lk — lanes differ only via lk, folded into the initial state)
-    imp_cj += dk;
-    while (imp_cj >= d.c) {
-      imp_cj -= d.c;
-      ++imp_cell;
-      ++imp_ds;
-      if (imp_ds == d.s) {
-        imp_ds = 0;
-        ++imp_dr;
-      }
-    }
-  };
-  auto stage = [&](int buf, int k0) {
-    bf16* lds_a = lds + buf * (BM + BN) * BK;
-    bf16* lds_b = lds_a + BM * BK;
-#pragma unroll
-    for (int i = 0; i < A_INSTRS; ++i) {
-      int row = (wave * A_INSTRS + i) * 8 + lrow;
-      int grow = m0 + row;
-      if (grow >= M) grow = M - 1;  // clamp: garbage rows masked at store
-      const bf16* src;
-      if constexpr (IMPLICIT) {
-        if (imp_cell >= d.r * d.s) {
-          src = zero;
-        } else {
-          int hh = imp_hh0[i] + imp_dr;
-          int ww = imp_ww0[i] + imp_ds;
-          src = (hh >= 0 && hh < d.h && ww >= 0 && ww < d.w)
-                    ? A + (imp_rowbase[i] + ((i64)hh * d.w + ww) * d.c +
-                           imp_cj)
-                    : zero;
-        }
-      } else {
-        src = A + (size_t)grow * K + k0 + lk;
-      }
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) uint32_t*)src,
-          (__attribute__((address_space(3)))
-               uint32_t*)(lds_a + (size_t)(wave * A_INSTRS + i) * 8 * BK),
-          16, 0, 0);
-    }
-#pragma unroll
-    for (int i = 0; i < B_INSTRS; ++i) {
-      int row = (wave * B_INSTRS + i) * 8 + lrow;
-      const bf16* src = B + (size_t)(n0 + row) * K + k0 + lk;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) uint32_t*)src,
-          (__attribute__((address_space(3)))
-               uint32_t*)(lds_b + (size_t)(wave * B_INSTRS + i) * 8 * BK),
-          16, 0, 0);
-    }
-  };
+  TileStager<BM, BN, IMPLICIT, FAST> st;
+  st.init(A, B, M, K, m0, n0, wave, lane, 0, d);
+  bf16x8 res[FM][FN / 2] = {};
 
   int ksteps = K / BK;
-  stage(0, 0);
-  for (int ks = 0; ks < ksteps; ++ks) {
+  st.issue(lds, wave, A, d, zero);
+  for (int ks = 0; ks + 1 < ksteps; ++ks) {
     int buf = ks & 1;
     // prefetch next while computing current
     __builtin_amdgcn_s_waitcnt(/*vmcnt(0) lgkmcnt(0)*/ 0);
     __syncthreads();
-    if (ks + 1 < ksteps) {
-      if constexpr (IMPLICIT) imp_advance(BK);
-      stage(buf ^ 1, (ks + 1) * BK);
-    }
-
-    const bf16* lds_a = lds + buf * (BM + BN) * BK;
-    const bf16* lds_b = lds_a + BM * BK;
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {  // two K=32 chunks per BK
-      int kbase = kk * 32 + (lane >> 4) * 8;
-      bf16x8 afrag[FM], bfrag[FN];
-#pragma unroll
-      for (int i = 0; i < FM; ++i) {
-        int row = wrow * (BM / WM) + i * 16 + (lane & 15);
-        afrag[i] = *reinterpret_cast<const bf16x8*>(
-            lds_a + (size_t)row * BK + kbase);
-      }
-#pragma unroll
-      for (int j = 0; j < FN; ++j) {
-        int col = wcol * (BN / WN) + j * 16 + (lane & 15);
-        bfrag[j] = *reinterpret_cast<const bf16x8*>(
-            lds_b + (size_t)col * BK + kbase);
-      }
-#pragma unroll
-      for (int i = 0; i < FM; ++i)
-#pragma unroll
-        for (int j = 0; j < FN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              afrag[i], bfrag[j], acc[i][j], 0, 0, 0);
-    }
+    st.advance(d);
+    st.issue(lds + (buf ^ 1) * (BM + BN) * BK, wave, A, d, zero);
+    mfma_step<BM, BN, WM, WN>(acc, lds + buf * (BM + BN) * BK, wrow, wcol,
+                              lane);
     // No trailing barrier: the next iteration's leading waitcnt+barrier
     // orders everything, and a __syncthreads() here would drain the
     // in-flight LDS-DMA prefetch (vmcnt(0) in its fence).
   }
+  // Last step, peeled: no LDS-DMA is outstanding any more, so the tile's
+  // residual reads go out here and land under the step's MFMAs. (Inside
+  // the loop the loaded registers would be live around the back edge, and
+  // hipcc then waits vmcnt(0) for them in every step — draining the
+  // prefetch.)
+  __builtin_amdgcn_s_waitcnt(0);
+  __syncthreads();
+  if constexpr (RESIDUAL)
+    load_residual<FM, FN>(res, residual, M, N, m0, n0, wrow, wcol, lane);
+  mfma_step<BM, BN, WM, WN>(acc, lds + ((ksteps - 1) & 1) * (BM + BN) * BK,
+                            wrow, wcol, lane);
 
   // epilogue: D = act(acc * scale[col] + bias[col] [+ residual]), stored
   // coalesced via per-wave LDS transpose. The scratch overlays the staging
   // LDS (no extra LDS), so one barrier first: every wave must be done
   // reading its final fragments before any wave overwrites the buffer.
-  // Nothing is in flight here (the last iteration stages no prefetch), so
-  // this barrier drains nothing.
+  // No LDS-DMA is in flight here (the last iteration stages no prefetch);
+  // the barrier's fence only waits for the residual reads issued above.
   __syncthreads();
   constexpr int EP_STRIDE = BN / WN + 4;
   float* scratch =
       reinterpret_cast<float*>(lds) + (size_t)wave * 16 * EP_STRIDE;
-  epilogue_store<FM, FN, RELU, RESIDUAL>(acc, scratch, C, residual, M, N,
-                                         m0, n0, wrow, wcol, lane, scale,
-                                         bias);
+  epilogue_store<FM, FN, RELU, RESIDUAL>(acc, scratch, C, res, M, N, m0, n0,
+                                         wrow, wcol, lane, sc, bi);
 }
 
 // Small-K variant (K = 64: the DNN ops' 1x1 convolutions out of 64-channel
@@ -305,9 +439,15 @@ __global__ void __launch_bounds__(256, 2)
   constexpr int K = 64;
   constexpr int FM = BM / WM / 16;
   constexpr int FN = BN / WN / 16;
-  __shared__ bf16 lds_b[BN * K];
-  __shared__ bf16 lds_a[2 * BM * K];
-  __shared__ float lds_ep[4 * 16 * (BN / WN + 4)];
+  // ONE __shared__ array for B, the two A buffers and the epilogue
+  // scratch: with several LDS objects next to an LDS-DMA target hipcc puts
+  // s_waitcnt vmcnt(0) in front of the first ds_read of every tile, which
+  // drains the A prefetch issued just before it.
+  constexpr int EP_FLOATS = 4 * 16 * (BN / WN + 4);
+  __shared__ bf16 lds[BN * K + 2 * BM * K + EP_FLOATS * 2];
+  bf16* lds_b = lds;
+  bf16* lds_a = lds + BN * K;
+  float* lds_ep = reinterpret_cast<float*>(lds + BN * K + 2 * BM * K);
 
   int tid = threadIdx.x;
   int lane = tid & 63;
@@ -323,6 +463,12 @@ __global__ void __launch_bounds__(256, 2)
   int mt_end = min(mt0 + tiles_per_wg, ntiles_m);
   if (mt0 >= ntiles_m) return;
 
+  // the strip's scale/bias: once, before the M walk (retired by the first
+  // tile's vmcnt(0))
+  float sc[FN], bi[FN];
+  load_scale_bias<FN>(sc, bi, scale, bias,
+                      n0 + wcol * (FN * 16) + (lane & 15));
+
   const int lrow = lane >> 3;
   const int lk = (lane & 7) * 8;
   constexpr int B_INSTRS = BN / 8 / 4;
@@ -331,12 +477,8 @@ __global__ void __launch_bounds__(256, 2)
 #pragma unroll
   for (int i = 0; i < B_INSTRS; ++i) {
     int row = (wave * B_INSTRS + i) * 8 + lrow;
-    const bf16* src = B + (size_t)(n0 + row) * K + lk;
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) uint32_t*)src,
-        (__attribute__((address_space(3)))
-             uint32_t*)(lds_b + (size_t)(wave * B_INSTRS + i) * 8 * K),
-        16, 0, 0);
+    glds16(B + (size_t)(n0 + row) * K + lk,
+           lds_b + (size_t)(wave * B_INSTRS + i) * 8 * K);
   }
 
   auto stage_a = [&](int buf, int mt) {
@@ -347,12 +489,8 @@ __global__ void __launch_bounds__(256, 2)
       int row = (wave * A_INSTRS + i) * 8 + lrow;
       int grow = m0 + row;
       if (grow >= M) grow = M - 1;
-      const bf16* src = A + (size_t)grow * K + lk;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) uint32_t*)src,
-          (__attribute__((address_space(3)))
-               uint32_t*)(dst + (size_t)(wave * A_INSTRS + i) * 8 * K),
-          16, 0, 0);
+      glds16(A + (size_t)grow * K + lk,
+             dst + (size_t)(wave * A_INSTRS + i) * 8 * K);
     }
   };
 
@@ -396,10 +534,17 @@ __global__ void __launch_bounds__(256, 2)
 
     // Coalesced store through dedicated per-wave scratch (lds_a/lds_b stay
     // live — the next tile's A prefetch is in flight right now, and the
-    // wave-local lgkmcnt waits inside don't drain it).
+    // wave-local lgkmcnt waits inside don't drain it). The residual reads
+    // go out here, all at once, and not before the MFMAs: vmcnt retires in
+    // order, so waiting for them also waits for the A prefetch issued
+    // above, and that wait belongs after the MFMAs.
+    bf16x8 res[FM][FN / 2] = {};
+    if constexpr (RESIDUAL)
+      load_residual<FM, FN>(res, residual, M, N, mt * BM, n0, wrow, wcol,
+                            lane);
     epilogue_store<FM, FN, RELU, RESIDUAL>(
-        acc, lds_ep + (size_t)wave * 16 * (BN / WN + 4), C, residual, M, N,
-        mt * BM, n0, wrow, wcol, lane, scale, bias);
+        acc, lds_ep + (size_t)wave * 16 * (BN / WN + 4), C, res, M, N,
+        mt * BM, n0, wrow, wcol, lane, sc, bi);
     // No trailing barrier (see main kernel note): next iteration's leading
     // waitcnt+barrier is the only ordering needed, and keeping the A
     // prefetch un-drained across the epilogue is the whole point.
@@ -428,7 +573,103 @@ struct SplitkEp {
   int relu = 0;
 };
 
-template <int BM, int BN, int WM, int WN, bool IMPLICIT, bool ATOMIC>
+// One float4 quad of each split's partial ([split][M][N], quad at element
+// offset off). S > 0: the split count is a template argument and load()
+// issues all S loads back to back (independent loads, one wait); a runtime
+// loop of load-then-add is a chain of `splits` dependent HBM round trips.
+// S == 0 keeps that runtime loop for split counts above 6
+// (SCANNER_SPLITK_MAX). sum() adds in the fixed order every reduce variant
+// shares, split 0 first, so they agree bit for bit.
+template <int S>
+struct SplitPartials {
+  float4 p[S > 0 ? S : 1];
+  const float* base;
+  size_t stride;
+
+  __device__ inline void load(const float* __restrict__ partials,
+                              size_t split_stride, size_t off) {
+    base = partials + off;
+    stride = split_stride;
+#pragma unroll
+    for (int sp = 0; sp < S; ++sp)
+      p[sp] = *reinterpret_cast<const float4*>(base + sp * stride);
+  }
+
+  __device__ inline float4 sum(int splits) const {
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (S > 0) {
+#pragma unroll
+      for (int sp = 0; sp < S; ++sp) {
+        acc.x += p[sp].x;
+        acc.y += p[sp].y;
+        acc.z += p[sp].z;
+        acc.w += p[sp].w;
+      }
+    } else {
+      for (int sp = 0; sp < splits; ++sp) {
+        float4 v = *reinterpret_cast<const float4*>(base + sp * stride);
+        acc.x += v.x;
+        acc.y += v.y;
+        acc.z += v.z;
+        acc.w += v.w;
+      }
+    }
+    return acc;
+  }
+};
+
+// Epilogue operands of one output quad (4 consecutive columns of one row;
+// N % 64 == 0, so a quad never straddles a row): one 16-byte load each for
+// scale and bias, one 8-byte load for the residual, each behind a uniform
+// test (has_res is a compile-time constant in the reduce kernels) and
+// independent of everything else the thread loads. Callers issue their
+// partial loads first, so one wait covers all of a quad's reads.
+struct QuadOperands {
+  float4 sc, bi;
+  uint2 res;
+};
+
+__device__ inline QuadOperands load_quad_operands(
+    const float* __restrict__ scale, const float* __restrict__ bias,
+    const bf16* __restrict__ residual, bool has_res, int col, size_t off) {
+  QuadOperands o;
+  o.sc = make_float4(1.f, 1.f, 1.f, 1.f);
+  o.bi = make_float4(0.f, 0.f, 0.f, 0.f);
+  o.res = make_uint2(0u, 0u);
+  if (scale) o.sc = *reinterpret_cast<const float4*>(scale + col);
+  if (bias) o.bi = *reinterpret_cast<const float4*>(bias + col);
+  if (has_res) o.res = *reinterpret_cast<const uint2*>(residual + off);
+  return o;
+}
+
+// v * scale, + bias, + residual, ReLU, bf16 — as separate roundings (no
+// fused multiply-add), which is what the split-K paths have always
+// computed; one 8-byte store.
+__device__ inline void store_quad(float4 a, const QuadOperands& o,
+                                  bool has_scale, bool has_bias,
+                                  bool has_res, bool relu,
+                                  bf16* __restrict__ dst) {
+#pragma clang fp contract(off)
+  float v4[4] = {a.x, a.y, a.z, a.w};
+  float s4[4] = {o.sc.x, o.sc.y, o.sc.z, o.sc.w};
+  float b4[4] = {o.bi.x, o.bi.y, o.bi.z, o.bi.w};
+  bf16 r4[4];
+  *reinterpret_cast<uint2*>(r4) = o.res;
+  bf16 o4[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    float v = v4[k];
+    if (has_scale) v *= s4[k];
+    if (has_bias) v += b4[k];
+    if (has_res) v += bf16_to_f32(r4[k]);
+    if (relu) v = v > 0.f ? v : 0.f;
+    o4[k] = f32_to_bf16(v);
+  }
+  *reinterpret_cast<uint64_t*>(dst) = *reinterpret_cast<const uint64_t*>(o4);
+}
+
+template <int BM, int BN, int WM, int WN, bool IMPLICIT, bool FAST,
+          bool ATOMIC>
 __global__ void __launch_bounds__(256, 2)
     gemm_bf16_splitk_kernel(const bf16* __restrict__ A,
                             const bf16* __restrict__ B, int M, int N, int K,
@@ -463,91 +704,27 @@ __global__ void __launch_bounds__(256, 2)
 #pragma unroll
     for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  constexpr int A_INSTRS = BM / 8 / 4;
-  constexpr int B_INSTRS = BN / 8 / 4;
-  auto stage = [&](int buf, int k0) {
-    const int lrow = lane >> 3;
-    const int lk = (lane & 7) * 8;
-    bf16* lds_a = lds + buf * (BM + BN) * BK;
-    bf16* lds_b = lds_a + BM * BK;
-#pragma unroll
-    for (int i = 0; i < A_INSTRS; ++i) {
-      int row = (wave * A_INSTRS + i) * 8 + lrow;
-      int grow = m0 + row;
-      if (grow >= M) grow = M - 1;
-      const bf16* src;
-      if constexpr (IMPLICIT) {
-        int k = k0 + lk;
-        int cell = k / d.c;
-        int cj = k - cell * d.c;
-        if (cell >= d.r * d.s) {
-          src = zero;
-        } else {
-          int dr = cell / d.s, ds = cell - dr * d.s;
-          int q = grow % d.ow;
-          int t = grow / d.ow;
-          int p = t % d.oh;
-          int nn = t / d.oh;
-          int hh = p * d.stride - d.pad + dr;
-          int ww = q * d.stride - d.pad + ds;
-          src = (hh >= 0 && hh < d.h && ww >= 0 && ww < d.w)
-                    ? A + ((((i64)nn * d.h + hh) * d.w + ww) * d.c + cj)
-                    : zero;
-        }
-      } else {
-        src = A + (size_t)grow * K + k0 + lk;
-      }
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) uint32_t*)src,
-          (__attribute__((address_space(3)))
-               uint32_t*)(lds_a + (size_t)(wave * A_INSTRS + i) * 8 * BK),
-          16, 0, 0);
-    }
-#pragma unroll
-    for (int i = 0; i < B_INSTRS; ++i) {
-      int row = (wave * B_INSTRS + i) * 8 + lrow;
-      const bf16* src = B + (size_t)(n0 + row) * K + k0 + lk;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) uint32_t*)src,
-          (__attribute__((address_space(3)))
-               uint32_t*)(lds_b + (size_t)(wave * B_INSTRS + i) * 8 * BK),
-          16, 0, 0);
-    }
-  };
+  // the same staging as the tile kernel, started at this split's first k
+  TileStager<BM, BN, IMPLICIT, FAST> st;
+  st.init(A, B, M, K, m0, n0, wave, lane, ks_begin * BK, d);
 
-  stage(0, ks_begin * BK);
+  st.issue(lds, wave, A, d, zero);
   for (int ks = ks_begin; ks < ks_end; ++ks) {
     int buf = (ks - ks_begin) & 1;
     __builtin_amdgcn_s_waitcnt(0);
     __syncthreads();
-    if (ks + 1 < ks_end) stage(buf ^ 1, (ks + 1) * BK);
-
-    const bf16* lds_a = lds + buf * (BM + BN) * BK;
-    const bf16* lds_b = lds_a + BM * BK;
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      int kbase = kk * 32 + (lane >> 4) * 8;
-      bf16x8 afrag[FM], bfrag[FN];
-#pragma unroll
-      for (int i = 0; i < FM; ++i) {
-        int row = wrow * (BM / WM) + i * 16 + (lane & 15);
-        afrag[i] = *reinterpret_cast<const bf16x8*>(
-            lds_a + (size_t)row * BK + kbase);
-      }
-#pragma unroll
-      for (int j = 0; j < FN; ++j) {
-        int col = wcol * (BN / WN) + j * 16 + (lane & 15);
-        bfrag[j] = *reinterpret_cast<const bf16x8*>(
-            lds_b + (size_t)col * BK + kbase);
-      }
-#pragma unroll
-      for (int i = 0; i < FM; ++i)
-#pragma unroll
-        for (int j = 0; j < FN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              afrag[i], bfrag[j], acc[i][j], 0, 0, 0);
+    if (ks + 1 < ks_end) {
+      st.advance(d);
+      st.issue(lds + (buf ^ 1) * (BM + BN) * BK, wave, A, d, zero);
     }
-    __syncthreads();
+    mfma_step<BM, BN, WM, WN>(acc, lds + buf * (BM + BN) * BK, wrow, wcol,
+                              lane);
+    // No trailing barrier, as in the tile kernel: the next iteration's
+    // leading waitcnt+barrier comes before anything is staged into the
+    // buffer read here, and a __syncthreads() at this point would drain
+    // the in-flight LDS-DMA prefetch (vmcnt(0) in its fence) and cost a
+    // second barrier per step. Nothing after the loop reuses the LDS
+    // without a barrier of its own.
   }
 
   if constexpr (ATOMIC) {
@@ -593,46 +770,66 @@ __global__ void __launch_bounds__(256, 2)
       // store. The counter is restored to 0 for the next launch that
       // reuses this scratch (launches on the stream are ordered, and
       // hipGraph replays see the same all-zero state).
+      // The "last arriver" flag overlays the staging LDS (every wave is
+      // past its last fragment read at the barrier below): a second
+      // __shared__ object beside the LDS-DMA target makes hipcc wait
+      // vmcnt(0) before the first ds_read of every K step, which drains
+      // the prefetch just issued.
       __threadfence();
       __syncthreads();
-      __shared__ unsigned int s_old;
+      unsigned int& s_old = *reinterpret_cast<unsigned int*>(lds);
       if (tid == 0) s_old = atomicAdd(ep.counters + tile, 1u);
       __syncthreads();
       if (s_old != (unsigned int)ep.splits - 1) return;
       __threadfence();  // acquire: other splits' partials now visible
       int rows = min(BM, M - m0);
       constexpr int Q = BN / 4;  // float4 quads per tile row
+      const size_t mn = (size_t)M * N;
       for (int idx = tid; idx < rows * Q; idx += 256) {
         int r = idx / Q, q = idx - r * Q;
         size_t base = (size_t)(m0 + r) * N + n0 + q * 4;
-        float4 av = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int sp = 0; sp < ep.splits; ++sp) {
-          float4 p = *reinterpret_cast<const float4*>(
-              partials + (size_t)sp * M * N + base);
-          av.x += p.x;
-          av.y += p.y;
-          av.z += p.z;
-          av.w += p.w;
+        auto finish = [&](auto nsplit) {
+          SplitPartials<decltype(nsplit)::value> sp;
+          sp.load(partials, mn, base);
+          QuadOperands o =
+              load_quad_operands(ep.scale, ep.bias, ep.residual,
+                                 ep.residual != nullptr, n0 + q * 4, base);
+          store_quad(sp.sum(ep.splits), o, ep.scale != nullptr,
+                     ep.bias != nullptr, ep.residual != nullptr,
+                     ep.relu != 0, ep.C + base);
+        };
+        switch (ep.splits) {
+          case 2: finish(std::integral_constant<int, 2>{}); break;
+          case 3: finish(std::integral_constant<int, 3>{}); break;
+          case 4: finish(std::integral_constant<int, 4>{}); break;
+          case 5: finish(std::integral_constant<int, 5>{}); break;
+          case 6: finish(std::integral_constant<int, 6>{}); break;
+          default: finish(std::integral_constant<int, 0>{});
         }
-        float v4[4] = {av.x, av.y, av.z, av.w};
-        bf16 o4[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          float v = v4[k];
-          int col = n0 + q * 4 + k;
-          if (ep.scale) v *= ep.scale[col];
-          if (ep.bias) v += ep.bias[col];
-          if (ep.residual) v += bf16_to_f32(ep.residual[base + k]);
-          if (ep.relu) v = v > 0.f ? v : 0.f;
-          o4[k] = f32_to_bf16(v);
-        }
-        *reinterpret_cast<uint64_t*>(ep.C + base) =
-            *reinterpret_cast<const uint64_t*>(o4);
       }
       if (tid == 0) ep.counters[tile] = 0;
     }
   }
 }
+
+// Quad index -> column without 64-bit division: one 32-bit modulo for the
+// thread's first quad (the grid is at most 4096 x 256 threads, so it fits
+// 32 bits whatever mn is), then an add and a conditional subtract per
+// grid stride.
+struct QuadColumn {
+  unsigned nq, cq, cstep;
+  __device__ inline QuadColumn(int N) {
+    nq = (unsigned)N / 4;
+    unsigned gs = gridDim.x * blockDim.x;
+    cq = (blockIdx.x * blockDim.x + threadIdx.x) % nq;
+    cstep = gs % nq;
+  }
+  __device__ inline int col() const { return (int)(cq * 4); }
+  __device__ inline void next() {
+    cq += cstep;
+    if (cq >= nq) cq -= nq;
+  }
+};
 
 template <bool RELU, bool RESIDUAL>
 __global__ void __launch_bounds__(256)
@@ -643,28 +840,23 @@ __global__ void __launch_bounds__(256)
                            bf16* __restrict__ C) {
   i64 quads = mn / 4;
   i64 gs = (i64)gridDim.x * blockDim.x;
+  QuadColumn qc(N);
   for (i64 q = (i64)blockIdx.x * blockDim.x + threadIdx.x; q < quads;
-       q += gs) {
+       q += gs, qc.next()) {
     i64 i = q * 4;
     float4 a4 = reinterpret_cast<const float4*>(acc)[q];
-    float v4[4] = {a4.x, a4.y, a4.z, a4.w};
-    bf16 o4[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      float v = v4[k];
-      int col = (int)((i + k) % N);
-      if (scale) v *= scale[col];
-      if (bias) v += bias[col];
-      if constexpr (RESIDUAL) v += bf16_to_f32(residual[i + k]);
-      if constexpr (RELU) v = v > 0.f ? v : 0.f;
-      o4[k] = f32_to_bf16(v);
-    }
-    *reinterpret_cast<uint64_t*>(C + i) =
-        *reinterpret_cast<const uint64_t*>(o4);
+    QuadOperands o = load_quad_operands(scale, bias, residual, RESIDUAL,
+                                        qc.col(), (size_t)i);
+    store_quad(a4, o, scale != nullptr, bias != nullptr, RESIDUAL, RELU,
+               C + i);
   }
 }
 
-template <bool RELU, bool RESIDUAL>
+// S: the split count when it is 2..6 (all partial loads independent), 0
+// for a runtime count (see SplitPartials). The grid covers every quad of a
+// split shape in one pass (tiles < 256 bounds mn below 4096 x 256 x 4),
+// so the grid-stride loop runs once; it stays for safety.
+template <bool RELU, bool RESIDUAL, int S>
 __global__ void __launch_bounds__(256)
     splitk_reduce_kernel(const float* __restrict__ partials, int splits,
                          i64 mn, int N, const float* __restrict__ scale,
@@ -676,36 +868,27 @@ __global__ void __launch_bounds__(256)
   // only ~2.2 TB/s on S x M x N partial streams.
   i64 quads = mn / 4;
   i64 gs = (i64)gridDim.x * blockDim.x;
+  QuadColumn qc(N);
   for (i64 q = (i64)blockIdx.x * blockDim.x + threadIdx.x; q < quads;
-       q += gs) {
+       q += gs, qc.next()) {
     i64 i = q * 4;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int sp = 0; sp < splits; ++sp) {
-      float4 p = reinterpret_cast<const float4*>(
-          partials + (size_t)sp * mn)[q];
-      acc.x += p.x;
-      acc.y += p.y;
-      acc.z += p.z;
-      acc.w += p.w;
-    }
-    float v4[4] = {acc.x, acc.y, acc.z, acc.w};
-    bf16 o4[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      float v = v4[k];
-      int col = (int)((i + k) % N);
-      if (scale) v *= scale[col];
-      if (bias) v += bias[col];
-      if constexpr (RESIDUAL) v += bf16_to_f32(residual[i + k]);
-      if constexpr (RELU) v = v > 0.f ? v : 0.f;
-      o4[k] = f32_to_bf16(v);
-    }
-    *reinterpret_cast<uint64_t*>(C + i) =
-        *reinterpret_cast<const uint64_t*>(o4);
+    SplitPartials<S> sp;
+    sp.load(partials, (size_t)mn, (size_t)i);
+    QuadOperands o = load_quad_operands(scale, bias, residual, RESIDUAL,
+                                        qc.col(), (size_t)i);
+    store_quad(sp.sum(splits), o, scale != nullptr, bias != nullptr,
+               RESIDUAL, RELU, C + i);
   }
 }
 
 const bf16* device_zero_chunk();
+
+// TileStager's FAST mode: every 64-wide K step lies inside one (r, s)
+// cell, one validity bit per tap fits a 32-bit word, and K has no padded
+// tail.
+bool conv_fast_path(const ConvDesc& d, int K) {
+  return d.c % 64 == 0 && d.r * d.s <= 32 && K == d.r * d.s * d.c;
+}
 
 constexpr size_t kSplitkCtrBytes = 4096;  // tile counters at the scratch tail
 
@@ -807,32 +990,30 @@ void launch_splitk(const GemmArgs& g, hipStream_t s, const GemmPlan& p,
       throw ScannerError(std::string("splitk memset failed: ") +
                          hipGetErrorString(e));
     }
-    if (dd) {
-      gemm_bf16_splitk_kernel<BM, BN, 2, 2, true, true>
-          <<<grid_main, 256, 0, s>>>(
-              (const bf16*)g.A, (const bf16*)g.B, g.M, g.N, g.K,
-              ksteps_per_split, (float*)g.splitk_scratch, *dd,
-              device_zero_chunk(), SplitkEp{});
-    } else {
-      gemm_bf16_splitk_kernel<BM, BN, 2, 2, false, true>
-          <<<grid_main, 256, 0, s>>>(
-              (const bf16*)g.A, (const bf16*)g.B, g.M, g.N, g.K,
-              ksteps_per_split, (float*)g.splitk_scratch, ConvDesc{},
-              nullptr, SplitkEp{});
-    }
-  } else if (dd) {
-    gemm_bf16_splitk_kernel<BM, BN, 2, 2, true, false>
-        <<<grid_main, 256, 0, s>>>(
-            (const bf16*)g.A, (const bf16*)g.B, g.M, g.N, g.K,
-            ksteps_per_split, (float*)g.splitk_scratch, *dd,
-            device_zero_chunk(), ep);
-  } else {
-    gemm_bf16_splitk_kernel<BM, BN, 2, 2, false, false>
-        <<<grid_main, 256, 0, s>>>(
-            (const bf16*)g.A, (const bf16*)g.B, g.M, g.N, g.K,
-            ksteps_per_split, (float*)g.splitk_scratch, ConvDesc{}, nullptr,
-            ep);
   }
+  auto main_kernel = [&](auto implicit, auto fast, auto atomic) {
+    constexpr bool kImplicit = decltype(implicit)::value;
+    gemm_bf16_splitk_kernel<BM, BN, 2, 2, kImplicit, decltype(fast)::value,
+                            decltype(atomic)::value>
+        <<<grid_main, 256, 0, s>>>(
+            (const bf16*)g.A, (const bf16*)g.B, g.M, g.N, g.K,
+            ksteps_per_split, (float*)g.splitk_scratch,
+            kImplicit ? *dd : ConvDesc{},
+            kImplicit ? device_zero_chunk() : nullptr,
+            decltype(atomic)::value ? SplitkEp{} : ep);
+  };
+  auto by_atomic = [&](auto implicit, auto fast) {
+    if (kAtomic)
+      main_kernel(implicit, fast, std::true_type{});
+    else
+      main_kernel(implicit, fast, std::false_type{});
+  };
+  if (!dd)
+    by_atomic(std::false_type{}, std::false_type{});
+  else if (conv_fast_path(*dd, g.K))
+    by_atomic(std::true_type{}, std::true_type{});
+  else
+    by_atomic(std::true_type{}, std::false_type{});
   e = hipGetLastError();
   if (e != hipSuccess) {
     throw ScannerError(std::string("splitk launch failed: ") +
@@ -850,10 +1031,21 @@ void launch_splitk(const GemmArgs& g, hipStream_t s, const GemmPlan& p,
                                 g.scale, g.bias, (const bf16*)g.residual,
                                 (bf16*)g.C);
     } else {
-      splitk_reduce_kernel<decltype(relu)::value, decltype(res)::value>
-          <<<grid, 256, 0, s>>>((const float*)g.splitk_scratch, splits, mn,
-                                g.N, g.scale, g.bias,
-                                (const bf16*)g.residual, (bf16*)g.C);
+      auto reduce = [&](auto nsplit) {
+        splitk_reduce_kernel<decltype(relu)::value, decltype(res)::value,
+                             decltype(nsplit)::value>
+            <<<grid, 256, 0, s>>>((const float*)g.splitk_scratch, splits, mn,
+                                  g.N, g.scale, g.bias,
+                                  (const bf16*)g.residual, (bf16*)g.C);
+      };
+      switch (splits) {
+        case 2: reduce(std::integral_constant<int, 2>{}); break;
+        case 3: reduce(std::integral_constant<int, 3>{}); break;
+        case 4: reduce(std::integral_constant<int, 4>{}); break;
+        case 5: reduce(std::integral_constant<int, 5>{}); break;
+        case 6: reduce(std::integral_constant<int, 6>{}); break;
+        default: reduce(std::integral_constant<int, 0>{});  // runtime count
+      }
     }
   };
   if (g.relu && g.residual)
@@ -919,7 +1111,8 @@ void launch_variant(const GemmArgs& g, hipStream_t s, const GemmPlan& p) {
   const int grid = p.grid;
   auto disp = [&](auto relu, auto res) {
     gemm_bf16_kernel<BM, BN, WM, WN, decltype(relu)::value,
-                     decltype(res)::value, false><<<grid, 256, 0, s>>>(
+                     decltype(res)::value, false, false>
+        <<<grid, 256, 0, s>>>(
         (const bf16*)g.A, (const bf16*)g.B, (bf16*)g.C, g.M, g.N, g.K,
         g.scale, g.bias, (const bf16*)g.residual, ConvDesc{}, nullptr);
   };
@@ -963,11 +1156,19 @@ void launch_conv_variant(const GemmArgs& g, const ConvDesc& d,
                          hipStream_t s, const GemmPlan& p) {
   const int grid = p.grid;
   const bf16* zero = device_zero_chunk();
-  auto disp = [&](auto relu, auto res) {
+  const bool fast = conv_fast_path(d, g.K);
+  auto launch = [&](auto relu, auto res, auto fast_t) {
     gemm_bf16_kernel<BM, BN, WM, WN, decltype(relu)::value,
-                     decltype(res)::value, true><<<grid, 256, 0, s>>>(
-        (const bf16*)g.A, (const bf16*)g.B, (bf16*)g.C, g.M, g.N, g.K,
-        g.scale, g.bias, (const bf16*)g.residual, d, zero);
+                     decltype(res)::value, true, decltype(fast_t)::value>
+        <<<grid, 256, 0, s>>>(
+            (const bf16*)g.A, (const bf16*)g.B, (bf16*)g.C, g.M, g.N, g.K,
+            g.scale, g.bias, (const bf16*)g.residual, d, zero);
+  };
+  auto disp = [&](auto relu, auto res) {
+    if (fast)
+      launch(relu, res, std::true_type{});
+    else
+      launch(relu, res, std::false_type{});
   };
   if (g.relu && g.residual)
     disp(std::true_type{}, std::true_type{});

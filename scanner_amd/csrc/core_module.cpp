@@ -4,6 +4,8 @@
 // by csrc/msgpack.h here).
 #include <dlfcn.h>
 
+#include <chrono>
+
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
@@ -635,6 +637,190 @@ PYBIND11_MODULE(_core, m) {
         },
         py::arg("frames"), py::arg("gop") = 16,
         py::arg("want") = std::vector<i64>{});
+  // ---- sink-side SVC encode (kernels/svc_encode.hip) ----
+  m.def("svc_packet_bound", &svc_packet_bound, py::arg("nbytes"));
+  // the oracle: svc_encode_cpu -> (stream bytes, per-frame packet sizes)
+  m.def("svc_cpu_encode",
+        [](py::array_t<u8, py::array::c_style | py::array::forcecast> frames,
+           i32 gop) {
+          SCA_CHECK(frames.ndim() == 4, "frames must be [N,H,W,C]");
+          SCA_CHECK(gop >= 1, "gop must be >= 1");
+          VideoMetadata vm;
+          std::vector<u8> stream;
+          svc_encode_cpu(frames.data(), frames.shape(0), (i32)frames.shape(1),
+                         (i32)frames.shape(2), (i32)frames.shape(3), gop,
+                         stream, vm);
+          return py::make_tuple(
+              py::bytes((const char*)stream.data(), stream.size()),
+              vm.sample_sizes);
+        },
+        py::arg("frames"), py::arg("gop") = 16);
+  // CPU decode of a packet stream given its per-frame sizes (checks the
+  // GPU encoder's output with the CPU decoder alone)
+  m.def("svc_cpu_decode",
+        [](py::bytes stream_b, std::vector<u64> sizes, i32 h, i32 w, i32 c,
+           i32 gop) {
+          std::string stream = stream_b;
+          SCA_CHECK(gop >= 1, "gop must be >= 1");
+          VideoMetadata vm;
+          vm.codec = "svc";
+          vm.height = h;
+          vm.width = w;
+          vm.channels = c;
+          vm.frame_type = FrameType::U8;
+          vm.num_frames = (i64)sizes.size();
+          u64 off = 0;
+          std::vector<i64> want;
+          for (size_t i = 0; i < sizes.size(); ++i) {
+            if (i % gop == 0) vm.keyframe_indices.push_back((i64)i);
+            vm.sample_offsets.push_back(off);
+            vm.sample_sizes.push_back(sizes[i]);
+            off += sizes[i];
+            want.push_back((i64)i);
+          }
+          SCA_CHECK(off == stream.size(), "sizes do not add up to the stream");
+          std::vector<std::vector<u8>> frames;
+          svc_decode_cpu((const u8*)stream.data(), stream.size(), vm, want,
+                         frames);
+          size_t fsize = (size_t)h * w * c;
+          py::array_t<u8> out({(i64)frames.size(), (i64)h, (i64)w, (i64)c});
+          for (size_t i = 0; i < frames.size(); ++i)
+            std::memcpy(out.mutable_data() + i * fsize, frames[i].data(),
+                        fsize);
+          return out;
+        },
+        py::arg("stream"), py::arg("sizes"), py::arg("h"), py::arg("w"),
+        py::arg("c"), py::arg("gop") = 16);
+  // The clip is uploaded as ONE contiguous device buffer (frame i at
+  // i*nbytes), so an odd nbytes gives misaligned frames. chunk > 0 splits
+  // the encode into consecutive calls of `chunk` frames, each predicting its
+  // first delta frame from the previous call's last frame — the executor's
+  // packet pattern.
+  m.def("svc_gpu_encode",
+        [](py::array_t<u8, py::array::c_style | py::array::forcecast> frames,
+           i32 gop, i64 chunk) {
+          SCA_CHECK(frames.ndim() == 4, "frames must be [N,H,W,C]");
+          SCA_CHECK(gop >= 1, "gop must be >= 1");
+          i64 n = frames.shape(0);
+          size_t fsize = (size_t)frames.shape(1) * frames.shape(2) *
+                         frames.shape(3);
+          DeviceHandle dev{DeviceType::GPU, 0};
+          std::vector<u8> stream;
+          std::vector<u64> sizes;
+          if (n == 0) {
+            return py::make_tuple(py::bytes(), sizes);
+          }
+          u8* d = new_buffer(dev, fsize * n);
+          try {
+            memcpy_buffer(d, dev, frames.data(), CPU_DEVICE, fsize * n);
+            i64 step = chunk > 0 ? chunk : n;
+            for (i64 s = 0; s < n; s += step) {
+              i64 e = std::min(n, s + step);
+              std::vector<const u8*> fp;
+              std::vector<u8> key;
+              for (i64 i = s; i < e; ++i) {
+                fp.push_back(d + (size_t)i * fsize);
+                key.push_back(i % gop == 0 ? 1 : 0);
+              }
+              svc_encode_gpu(fp, s > 0 ? d + (size_t)(s - 1) * fsize : nullptr,
+                             key, (u32)fsize, dev, stream, sizes);
+            }
+          } catch (...) {
+            delete_buffer(dev, d);
+            throw;
+          }
+          delete_buffer(dev, d);
+          return py::make_tuple(
+              py::bytes((const char*)stream.data(), stream.size()), sizes);
+        },
+        py::arg("frames"), py::arg("gop") = 16, py::arg("chunk") = 0);
+  // Seconds for `iters` encodes of n device-resident h*w*c frames, ending in
+  // a stream synchronise. mode "gpu": svc_encode_gpu including the D2H of
+  // the compressed bytes. mode "cpu": the host sink path — D2H of the raw
+  // frames into host memory, then svc_encode_cpu. clip "smooth" is a moving
+  // gradient (small widths), "noise" a seeded xorshift stream (width 8).
+  m.def("svc_encode_bench",
+        [](i32 h, i32 w, i32 c, i64 n, i32 iters, const std::string& mode,
+           const std::string& clip, u32 seed) {
+          SCA_CHECK(mode == "gpu" || mode == "cpu",
+                    "mode must be 'gpu' or 'cpu'");
+          SCA_CHECK(clip == "smooth" || clip == "noise",
+                    "clip must be 'smooth' or 'noise'");
+          size_t fsize = (size_t)h * w * c;
+          SCA_CHECK(n > 0 && fsize > 0 && iters > 0, "empty benchmark");
+          DeviceHandle dev{DeviceType::GPU, 0};
+          // one block buffer, as a kernel op's output batch would be
+          u8* d = new_block_buffer(dev, fsize * n, 1);
+          double secs = 0;
+          try {
+            {
+              std::vector<u8> host(fsize * n);
+              u32 x = seed * 2654435761u + 1u;
+              size_t p = 0;
+              for (i64 i = 0; i < n; ++i)
+                for (i32 y = 0; y < h; ++y)
+                  for (i32 xx = 0; xx < w; ++xx)
+                    for (i32 ch = 0; ch < c; ++ch, ++p) {
+                      if (clip == "noise") {
+                        x ^= x << 13; x ^= x >> 17; x ^= x << 5;
+                        host[p] = (u8)(x >> 24);
+                      } else {
+                        i64 v = ch % 3 == 0   ? xx + i * 2
+                                : ch % 3 == 1 ? y + i
+                                              : xx + y + i * 3;
+                        host[p] = (u8)((v + seed) & 0xff);
+                      }
+                    }
+              memcpy_buffer(d, dev, host.data(), CPU_DEVICE, fsize * n);
+            }
+            std::vector<const u8*> fp;
+            std::vector<u8> key;
+            for (i64 i = 0; i < n; ++i) {
+              fp.push_back(d + (size_t)i * fsize);
+              key.push_back(i % 16 == 0 ? 1 : 0);
+            }
+            py::gil_scoped_release rel;
+            auto t0 = std::chrono::steady_clock::now();
+            for (i32 it = 0; it < iters; ++it) {
+              std::vector<u8> stream;
+              if (mode == "gpu") {
+                std::vector<u64> sizes;
+                svc_encode_gpu(fp, nullptr, key, (u32)fsize, dev, stream,
+                               sizes);
+              } else {
+                // executor sink today: per-frame pinned host elements, one
+                // batched D2H, then concatenate + encode
+                std::vector<u8*> dst;
+                std::vector<size_t> sz;
+                for (i64 i = 0; i < n; ++i) {
+                  dst.push_back(new_buffer(CPU_DEVICE, fsize));
+                  sz.push_back(fsize);
+                }
+                memcpy_vec(dst, CPU_DEVICE, fp, dev, sz);
+                std::vector<u8> contig;
+                contig.reserve(fsize * n);
+                for (i64 i = 0; i < n; ++i) {
+                  contig.insert(contig.end(), dst[i], dst[i] + fsize);
+                  delete_buffer(CPU_DEVICE, dst[i]);
+                }
+                VideoMetadata vm;
+                svc_encode_cpu(contig.data(), n, h, w, c, 16, stream, vm);
+              }
+              sync_per_thread_stream();
+            }
+            secs = std::chrono::duration<double>(
+                       std::chrono::steady_clock::now() - t0)
+                       .count();
+          } catch (...) {
+            delete_buffer(dev, d);
+            throw;
+          }
+          delete_buffer(dev, d);
+          return secs;
+        },
+        py::arg("h"), py::arg("w"), py::arg("c"), py::arg("n"),
+        py::arg("iters") = 1, py::arg("mode") = "gpu",
+        py::arg("clip") = "smooth", py::arg("seed") = 0);
   m.def("span_cache_clear", &span_cache_clear);
   m.def("span_cache_set_budget", &span_cache_set_budget);
   // engine memory accounting (device -1 = CPU)

@@ -1,6 +1,7 @@
 #include "executor.h"
 
 #include <algorithm>
+#include <cstdlib>
 #include <set>
 
 #include "../hip_util.h"
@@ -20,6 +21,43 @@ Element element_to_device(const Element& e, DeviceHandle target, bool& copied) {
   copied = true;
   return out;
 }
+
+namespace {
+
+// Default of SCANNER_SVC_GPU_ENCODE when it is unset: on. Measured end to
+// end at 1080p (decode -> GPU Blur -> compressed output, 40 frames) the
+// GPU sink takes 0.112 s against 0.493 s for the host sink, far outside
+// the run-to-run spread of either (profiles/svc_encode.md).
+constexpr bool kSvcGpuEncodeDefault = true;
+
+// SCANNER_SVC_GPU_ENCODE: 1 encodes svc-compressed output columns whose
+// rows are on a GPU with kernels/svc_encode.hip, 0 keeps the host path
+// (raw D2H + svc_encode_cpu). Read per executor, i.e. per job run, so one
+// process can run both ways.
+bool read_svc_gpu_encode_switch() {
+  const char* e = std::getenv("SCANNER_SVC_GPU_ENCODE");
+  if (!e || !*e) return kSvcGpuEncodeDefault;
+  return std::atoi(e) != 0;
+}
+
+// Task-local state of one svc-compressed output column that is encoded on
+// the GPU packet by packet: the host stream and its growing metadata, plus
+// one retained reference to the last frame of the previous packet — the
+// prediction source of the next packet's first delta frame.
+struct SinkSvcEncode {
+  bool candidate = false;  // compress=svc, Video column, table sink
+  bool decided = false;    // device fixed at the column's first packet
+  bool on_gpu = false;
+  DeviceHandle dev{DeviceType::CPU, 0};
+  std::vector<u8> stream;
+  VideoMetadata vm;
+  size_t fsize = 0;
+  u8* prev = nullptr;
+};
+
+constexpr i64 kSinkGop = 16;  // same cadence as the host path's gop
+
+}  // namespace
 
 struct LocalExecutor::Instance {
   i32 idx = 0;
@@ -44,6 +82,7 @@ LocalExecutor::LocalExecutor(std::shared_ptr<Database> db, JobGraph graph,
   mc.gpu_pool_size = pp_.gpu_pool_size;
   mc.gpu_ids = gpu_ids_;
   init_memory_allocators(mc);
+  svc_gpu_encode_ = read_svc_gpu_encode_switch();
   db_key_ = std::hash<std::string>{}(db_->paths().root);
   if (!gpu_ids_.empty()) {
     size_t budget = pp_.span_cache_size;
@@ -716,6 +755,7 @@ void LocalExecutor::process_task(Instance& inst, const TaskDesc& t,
   // D2H happens per packet so it overlaps later compute).
   std::vector<std::vector<Element>> sink_cols(out_op.inputs.size());
   std::vector<std::vector<u8>> sink_owned(out_op.inputs.size());
+  std::vector<SinkSvcEncode> sink_enc(out_op.inputs.size());
 
   std::map<i32, std::vector<SvcItemState>> svc_states;
   std::vector<size_t> cursor(n, 0);
@@ -755,9 +795,37 @@ void LocalExecutor::process_task(Instance& inst, const TaskDesc& t,
         }
       }
     }
+    for (auto& enc : sink_enc) {
+      if (enc.prev) delete_buffer(enc.dev, enc.prev);
+      enc.prev = nullptr;
+    }
   };
 
   try {
+    // Sink-side codec annotations (OpColumn.compress_video; parity:
+    // reference compressed-output columns + PostEvaluateWorker encode,
+    // evaluate_worker.cpp:1329-1560).
+    std::map<std::string, std::string> compress;
+    if (!out_op.args.empty()) {
+      auto a = mp::decode(out_op.args);
+      auto& am = a.as_map();
+      auto cit = am.find("compress");
+      if (cit != am.end()) {
+        for (auto& kv : cit->second.as_map())
+          compress[kv.first] = kv.second.as_str();
+      }
+    }
+    if (svc_gpu_encode_ && job.sink.sink.empty() && inst.gpu.is_gpu()) {
+      const TableMetadata& table = out_tables_[t.job];
+      for (size_t c = 0; c < sink_enc.size() && c < table.columns.size();
+           ++c) {
+        auto cmp = compress.find(table.columns[c].name);
+        sink_enc[c].candidate = cmp != compress.end() &&
+                                cmp->second == "svc" &&
+                                table.columns[c].type == ColumnType::Video;
+      }
+    }
+
     init_sources(inst, t, plan, outs, svc_states, prep);
 
     i64 W = std::max<i64>(1, pp_.work_packet_size);
@@ -855,10 +923,85 @@ void LocalExecutor::process_task(Instance& inst, const TaskDesc& t,
           DeviceHandle gpu_src = CPU_DEVICE;
           for (size_t c = 0; c < op.inputs.size(); ++c) {
             auto& parent_map = outs[op.inputs[c].op][op.inputs[c].column];
+            SinkSvcEncode& enc = sink_enc[c];
+            if (enc.candidate && !enc.decided) {
+              // the column's device is fixed by its first packet
+              for (i64 row = ps; row < pe && !enc.decided; ++row) {
+                auto pit = parent_map.find(row);
+                SCA_CHECK(pit != parent_map.end(), "sink missing row");
+                if (pit->second.is_null) continue;
+                enc.decided = true;
+                enc.on_gpu = pit->second.device.is_gpu();
+                enc.dev = pit->second.device;
+              }
+              SCA_CHECK(enc.decided,
+                        "cannot codec-compress a column with null rows");
+            }
+            if (enc.on_gpu) {
+              // stream-encode on the device: the raw frames never cross
+              // the host link, only the packets they compress to
+              std::vector<const u8*> fp;
+              std::vector<u8> key;
+              for (i64 row = ps; row < pe; ++row) {
+                auto pit = parent_map.find(row);
+                SCA_CHECK(pit != parent_map.end(), "sink missing row");
+                const Element& e = pit->second;
+                SCA_CHECK(!e.is_null,
+                          "cannot codec-compress a column with null rows");
+                SCA_CHECK(e.is_frame && e.frame_info.type == FrameType::U8,
+                          "svc compression needs u8 frames");
+                SCA_CHECK(e.device == enc.dev,
+                          "compressed output column changed device within "
+                          "a task");
+                if (enc.vm.num_frames == 0 && fp.empty()) {
+                  enc.vm.codec = "svc";
+                  enc.vm.height = e.frame_info.shape[0];
+                  enc.vm.width = e.frame_info.shape[1];
+                  enc.vm.channels = e.frame_info.shape[2];
+                  enc.vm.frame_type = FrameType::U8;
+                  enc.fsize = e.size;
+                }
+                SCA_CHECK(e.size == enc.fsize,
+                          "svc compression needs uniform frame sizes");
+                i64 f = enc.vm.num_frames + (i64)fp.size();
+                key.push_back(f % kSinkGop == 0 ? 1 : 0);
+                fp.push_back(e.buffer);
+              }
+              std::vector<u64> pkt_sizes;
+              u64 off = enc.stream.size();
+              svc_encode_gpu(fp, enc.prev, key, (u32)enc.fsize, enc.dev,
+                             enc.stream, pkt_sizes);
+              for (size_t k = 0; k < fp.size(); ++k) {
+                if (key[k])
+                  enc.vm.keyframe_indices.push_back(enc.vm.num_frames +
+                                                    (i64)k);
+                enc.vm.sample_offsets.push_back(off);
+                enc.vm.sample_sizes.push_back(pkt_sizes[k]);
+                off += pkt_sizes[k];
+              }
+              enc.vm.num_frames += (i64)fp.size();
+              // keep the packet's last frame alive past its producer's
+              // free (the encode above returned synchronised, so the
+              // frame it replaces is no longer read)
+              u8* last = const_cast<u8*>(fp.back());
+              add_buffer_ref(enc.dev, last);
+              if (enc.prev) delete_buffer(enc.dev, enc.prev);
+              enc.prev = last;
+              i64 packed = 0;
+              for (u64 sz : pkt_sizes) packed += (i64)sz;
+              inst.profiler->increment("svc_gpu_encode_frames",
+                                       (i64)fp.size());
+              inst.profiler->increment(
+                  "sink_d2h_bytes", packed + (i64)(4 * pkt_sizes.size()));
+              continue;
+            }
             for (i64 row = ps; row < pe; ++row) {
               auto pit = parent_map.find(row);
               SCA_CHECK(pit != parent_map.end(), "sink missing row");
               Element e = pit->second;
+              SCA_CHECK(!(enc.decided && !e.is_null && e.device.is_gpu()),
+                        "compressed output column changed device within a "
+                        "task");
               if (e.is_null) {
                 Element ne;
                 ne.is_null = true;
@@ -890,6 +1033,9 @@ void LocalExecutor::process_task(Instance& inst, const TaskDesc& t,
           }
           if (!d2h_dst.empty()) {
             memcpy_vec(d2h_dst, CPU_DEVICE, d2h_src, gpu_src, d2h_sz);
+            i64 raw = 0;
+            for (size_t sz : d2h_sz) raw += (i64)sz;
+            inst.profiler->increment("sink_d2h_bytes", raw);
           }
           for (size_t c = 0; c < op.inputs.size(); ++c)
             for (i64 row = ps; row < pe; ++row)
@@ -999,21 +1145,15 @@ void LocalExecutor::process_task(Instance& inst, const TaskDesc& t,
       const TableMetadata& table = out_tables_[t.job];
       auto& cols = sink_cols;
       auto& owned = sink_owned;
-      // Sink-side codec annotations (OpColumn.compress_video; parity:
-      // reference compressed-output columns + PostEvaluateWorker encode,
-      // evaluate_worker.cpp:1329-1560).
-      std::map<std::string, std::string> compress;
-      if (!out_op.args.empty()) {
-        auto a = mp::decode(out_op.args);
-        auto& am = a.as_map();
-        auto cit = am.find("compress");
-        if (cit != am.end()) {
-          for (auto& kv : cit->second.as_map())
-            compress[kv.first] = kv.second.as_str();
-        }
-      }
       auto write_col = [&](size_t c) {
         const std::string& cname = table.columns[c].name;
+        if (sink_enc[c].on_gpu) {
+          // encoded packet by packet on the device; only the write is left
+          SinkSvcEncode& enc = sink_enc[c];
+          inst.profiler->increment("io_write_bytes", (i64)enc.stream.size());
+          write_video_item(*db_, table, cname, t.task, enc.stream, enc.vm);
+          return;
+        }
         auto cmp = compress.find(cname);
         if (cmp != compress.end() &&
             table.columns[c].type == ColumnType::Video) {

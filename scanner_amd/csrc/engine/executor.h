@@ -152,6 +152,9 @@ class LocalExecutor {
   std::vector<TableMetadata> out_tables_;   // per job
   std::vector<std::vector<i64>> task_rows_; // per job: cumulative task ends
   bool prepared_ = false;
+  // SCANNER_SVC_GPU_ENCODE as read when this executor (one job run) was
+  // created: encode svc-compressed GPU output columns on the device.
+  bool svc_gpu_encode_ = false;
 
   std::atomic<i64> tasks_done_{0};
   std::vector<std::unique_ptr<Instance>> instances_;

@@ -348,7 +348,12 @@ void destroy_memory_allocators() {
     std::lock_guard<std::mutex> l(g_mem.mu);
     for (auto& kv : g_mem.gpus) gpu_ids.push_back(kv.first);
     g_mem.gpus.clear();
-    g_mem.cpu = DeviceAllocators{};
+    // reverse construction order: the pool returns its slab through the
+    // system allocator, so it has to go first (a whole-struct assignment
+    // resets `system` before `pool`)
+    g_mem.cpu.block.reset();
+    g_mem.cpu.pool.reset();
+    g_mem.cpu.system.reset();
     g_mem.initialized = false;
   }
   // Sanitizer affordance (parity: the reference's SystemAllocator dtor

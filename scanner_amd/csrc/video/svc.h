@@ -76,6 +76,24 @@ std::vector<Element> svc_decode_gpu_dev(const u8* stream_dev, u64 dev_lo,
                                         const std::vector<i64>& want,
                                         DeviceHandle dev);
 
+// Worst-case packet size of an nbytes frame: every group at width 8, i.e.
+// 20 + 4*nsuper + pad4(ngroups) + 32*ngroups. Sizes the GPU encoder's
+// per-frame staging stride.
+u64 svc_packet_bound(u32 nbytes);
+
+// GPU encode (kernels/svc_encode.hip): encode n device-resident u8 frames
+// (frames[i] = device pointer, nbytes each, no alignment required) as
+// packets appended to `stream`. key[i] says whether frame i is a keyframe;
+// delta frames predict from frames[i-1], and frame 0, if delta, from `prev`.
+// Appends one entry per frame to `sizes`. The bytes are identical to what
+// svc_encode_cpu produces for the same frames and key pattern. At most 16
+// frames are staged on the device at a time; only compressed bytes and the
+// per-frame sizes cross to the host. Runs on the calling thread's HIP
+// stream and returns synchronised.
+void svc_encode_gpu(const std::vector<const u8*>& frames, const u8* prev,
+                    const std::vector<u8>& key, u32 nbytes, DeviceHandle dev,
+                    std::vector<u8>& stream, std::vector<u64>& sizes);
+
 struct SvcPacketView {
   bool is_key = false;
   u32 nbytes = 0;

@@ -187,6 +187,12 @@ SvcPacketView svc_parse_packet(const u8* pkt, size_t size) {
   return v;
 }
 
+u64 svc_packet_bound(u32 nbytes) {
+  u64 ngroups = ((u64)nbytes + 31) / 32;
+  u64 nsuper = (ngroups + 127) / 128;
+  return 20 + 4 * nsuper + (ngroups + 3) / 4 * 4 + 32 * ngroups;
+}
+
 void svc_encode_cpu(const u8* frames, i64 n, i32 h, i32 w, i32 c, i32 gop,
                     std::vector<u8>& stream, VideoMetadata& vm) {
   u32 nbytes = (u32)((i64)h * w * c);

@@ -1,0 +1,236 @@
+"""GPU SVC encoder (kernels/svc_encode.hip) and the executor's sink path
+that uses it. The contract is byte identity with svc_encode_cpu: there is no
+tolerance anywhere in this file."""
+import functools
+
+import numpy as np
+import pytest
+
+import scanner_amd as sp
+from scanner_amd import FrameType, _core, register_python_op
+from conftest import make_smooth_video, make_video
+
+pytestmark = pytest.mark.gpu
+
+# (N,H,W,C): the smallest shape at which each mechanism can break
+SHAPES = [
+    (3, 1, 3, 3),        # nbytes=9: one group, all tail
+    (18, 5, 7, 3),       # nbytes=105: 4 groups, 9-byte tail, odd stride so
+                         # frames are misaligned; N crosses the 16-frame key
+                         # and the 16-frame chunk
+    (5, 37, 45, 3),      # 157 groups: 2 supergroups, 2nd partial, 3-byte tail
+    (4, 32, 128, 1),     # exactly one full supergroup, no tail
+    (3, 96, 128, 3),     # exactly 9 full supergroups
+    (2, 1080, 1920, 3),  # 1519 supergroups: more than one scan step
+]
+CONTENTS = ["smooth", "noise", "constant", "alternate", "widths"]
+
+
+def residual_for_bits(b):
+    """A residual whose zigzag code needs exactly b bits: 0 -> 0, -1 -> 1,
+    2^(b-2) -> 2^(b-1) for b >= 2."""
+    return 0 if b == 0 else (-1 if b == 1 else 1 << (b - 2))
+
+
+def crafted_bits(shape):
+    n = shape[0]
+    ngroups = (int(np.prod(shape[1:])) + 31) // 32
+    f, g = np.mgrid[0:n, 0:ngroups]
+    return (g + f) % 9
+
+
+def crafted_widths_clip(shape, gop):
+    """Group g of frame f is constant and needs exactly (g + f) % 9 bits:
+    a key group holds 128 + r (first residual r, the rest 0), a delta group
+    the previous frame's value + r (every residual r)."""
+    n = shape[0]
+    nbytes = int(np.prod(shape[1:]))
+    bits = crafted_bits(shape)
+    r = np.vectorize(residual_for_bits)(bits)
+    vals = np.zeros(bits.shape, np.int64)
+    for f in range(n):
+        vals[f] = (128 if f % gop == 0 else vals[f - 1]) + r[f]
+    flat = np.repeat(vals % 256, 32, axis=1)[:, :nbytes]
+    return flat.astype(np.uint8).reshape(shape)
+
+
+@functools.lru_cache(maxsize=None)
+def clip(shape, content, gop=16):
+    n, h, w, c = shape
+    if content == "smooth":
+        f = make_smooth_video(n=n, h=h, w=w)[..., :c]
+    elif content == "noise":
+        f = make_video(n=n, h=h, w=w, c=c, seed=11)
+    elif content == "constant":
+        f = np.full(shape, 77, np.uint8)
+    elif content == "alternate":
+        f = np.zeros(shape, np.uint8)
+        f[1::2] = 128
+    else:
+        f = crafted_widths_clip(shape, gop)
+    f = np.ascontiguousarray(f)
+    f.setflags(write=False)
+    return f
+
+
+@functools.lru_cache(maxsize=None)
+def cpu_reference(shape, content, gop=16):
+    """(stream, sizes) of the oracle, computed once per case."""
+    return _core.svc_cpu_encode(clip(shape, content, gop), gop)
+
+
+def stream_widths(stream, sizes, nbytes):
+    """Per-packet width[] arrays parsed out of a packet stream."""
+    ngroups = (nbytes + 31) // 32
+    nsuper = (ngroups + 127) // 128
+    buf = np.frombuffer(stream, np.uint8)
+    out, off = [], 0
+    for s in sizes:
+        w0 = off + 20 + 4 * nsuper
+        out.append(buf[w0:w0 + ngroups])
+        off += s
+    return np.stack(out)
+
+
+def check_case(shape, content, gop=16, chunk=0):
+    frames = clip(shape, content, gop)
+    _, h, w, c = shape
+    ref_stream, ref_sizes = cpu_reference(shape, content, gop)
+    if content == "widths":
+        # a condition on the inputs, checked on the CPU stream alone
+        got_w = stream_widths(ref_stream, ref_sizes, h * w * c)
+        np.testing.assert_array_equal(got_w, crafted_bits(shape))
+        if got_w.size >= 9:
+            assert set(np.unique(got_w)) == set(range(9))
+    # fixture sanity: the oracle stream decodes (on the GPU) to the input
+    np.testing.assert_array_equal(
+        _core.svc_gpu_roundtrip(frames, gop, []), frames)
+    stream, sizes = _core.svc_gpu_encode(frames, gop, chunk)
+    assert sizes == ref_sizes
+    assert stream == ref_stream
+    np.testing.assert_array_equal(
+        _core.svc_cpu_decode(stream, sizes, h, w, c, gop), frames)
+
+
+@pytest.mark.parametrize("content", CONTENTS)
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_encode_matches_cpu(shape, content):
+    check_case(shape, content)
+
+
+@pytest.mark.parametrize("gop", [1, 5, 16])
+@pytest.mark.parametrize("content", ["smooth", "noise", "widths"])
+def test_encode_gop(gop, content):
+    check_case((18, 5, 7, 3), content, gop=gop)
+
+
+@pytest.mark.parametrize("chunk", [1, 5, 7])
+@pytest.mark.parametrize("content", ["smooth", "noise", "widths"])
+def test_encode_chunked_equals_unchunked(chunk, content):
+    """Prediction chains cross call boundaries and keyframes fall
+    mid-chunk — the executor's packet pattern."""
+    check_case((18, 5, 7, 3), content, gop=16, chunk=chunk)
+
+
+def test_encode_worst_case_fills_bound():
+    """All-zero keyframes: every packet is exactly svc_packet_bound long, so
+    the staging stride is used to its last byte."""
+    frames = np.zeros((3, 37, 45, 3), np.uint8)
+    stream, sizes = _core.svc_gpu_encode(frames, 1, 0)
+    assert sizes == [_core.svc_packet_bound(37 * 45 * 3)] * 3
+    assert (stream, sizes) == tuple(_core.svc_cpu_encode(frames, 1))
+
+
+def test_encode_deterministic():
+    frames = clip((5, 37, 45, 3), "noise")
+    first = _core.svc_gpu_encode(frames, 16, 0)
+    for _ in range(3):
+        assert _core.svc_gpu_encode(frames, 16, 0) == first
+
+
+# ---------------- executor sink ----------------
+
+N, H, W = 40, 48, 64
+RAW = N * H * W * 3
+
+
+def run_blur(sc, monkeypatch, switch, name, frames):
+    monkeypatch.setenv("SCANNER_SVC_GPU_ENCODE", switch)
+    video = sp.NamedVideoStream(sc, name + "_in", frames=frames, codec="svc")
+    frame = sc.io.Input([video])
+    blur = sc.ops.Blur(frame=frame, kernel_size=3, device=sp.DeviceType.GPU)
+    blur.compress_video()
+    out = sp.NamedStream(sc, name)
+    # one task, 8 packets of 5, keyframes at 0, 16 and 32 mid-packet
+    prof = sc.run(sc.io.Output(blur, [out]), sp.PerfParams.manual(5, 40),
+                  cache_mode=sp.CacheMode.Overwrite, gpu_ids=[0])
+    got = np.stack(list(sp.NamedVideoStream(sc, name).load()))
+    return got, prof.counters()
+
+
+def test_pipeline_gpu_sink_matches_host_sink(sc, monkeypatch):
+    frames = make_smooth_video(n=N, h=H, w=W)
+    on, c_on = run_blur(sc, monkeypatch, "1", "enc_on", frames)
+    off, c_off = run_blur(sc, monkeypatch, "0", "enc_off", frames)
+    assert on.shape == (N, H, W, 3)
+    np.testing.assert_array_equal(on, off)
+    assert c_on["io_write_bytes"] == c_off["io_write_bytes"]
+    assert c_on.get("svc_gpu_encode_frames", 0) == N
+    assert 0 < c_on["sink_d2h_bytes"] < RAW
+    assert c_off.get("svc_gpu_encode_frames", 0) == 0
+    assert c_off["sink_d2h_bytes"] == RAW
+
+
+@register_python_op(name="SvcEncInvert")
+def svc_enc_invert(frame: FrameType) -> FrameType:
+    return 255 - frame
+
+
+def run_two_columns(sc, monkeypatch, switch, name, frames):
+    """Two svc-compressed output columns written by the save fan-out
+    threads. Every u8 GPU frame op names its output "frame" and an Output
+    takes each column name once, so the second column comes from a CPU op:
+    with the switch on, one column is encoded on the device and one on the
+    host, each from its own per-column state."""
+    monkeypatch.setenv("SCANNER_SVC_GPU_ENCODE", switch)
+    video = sp.NamedVideoStream(sc, name + "_in", frames=frames, codec="svc")
+    frame = sc.io.Input([video])
+    blur = sc.ops.Blur(frame=frame, kernel_size=3, device=sp.DeviceType.GPU)
+    blur.compress_video()
+    inv = sc.ops.SvcEncInvert(frame=frame)
+    inv.compress_video()
+    out = sp.NamedStream(sc, name)
+    prof = sc.run(sc.io.Output([blur, inv], [out]),
+                  sp.PerfParams.manual(5, 40),
+                  cache_mode=sp.CacheMode.Overwrite, gpu_ids=[0])
+    cols = [np.stack(list(sp.NamedVideoStream(sc, name, column=cn).load()))
+            for cn in ("frame", "out")]
+    return cols, prof.counters()
+
+
+def test_pipeline_two_compressed_columns(sc, monkeypatch):
+    frames = make_smooth_video(n=N, h=H, w=W)
+    on, c_on = run_two_columns(sc, monkeypatch, "1", "enc2_on", frames)
+    off, c_off = run_two_columns(sc, monkeypatch, "0", "enc2_off", frames)
+    for a, b in zip(on, off):
+        assert a.shape == (N, H, W, 3)
+        np.testing.assert_array_equal(a, b)
+    np.testing.assert_array_equal(on[1], 255 - frames)
+    assert c_on["io_write_bytes"] == c_off["io_write_bytes"]
+    assert c_on.get("svc_gpu_encode_frames", 0) == N
+    assert c_off.get("svc_gpu_encode_frames", 0) == 0
+
+
+def test_pipeline_null_row_still_rejected(sc, monkeypatch):
+    monkeypatch.setenv("SCANNER_SVC_GPU_ENCODE", "1")
+    frames = make_smooth_video(n=8, h=H, w=W)
+    video = sp.NamedVideoStream(sc, "enc_null_in", frames=frames, codec="svc")
+    frame = sc.io.Input([video])
+    blur = sc.ops.Blur(frame=frame, kernel_size=3, device=sp.DeviceType.GPU)
+    spaced = sc.streams.RepeatNull(blur, [2])
+    spaced.compress_video()
+    out = sp.NamedStream(sc, "enc_null_out")
+    with pytest.raises(Exception,
+                       match="cannot codec-compress a column with null rows"):
+        sc.run(sc.io.Output(spaced, [out]), sp.PerfParams.manual(4, 16),
+               cache_mode=sp.CacheMode.Overwrite, gpu_ids=[0])

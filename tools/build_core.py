@@ -40,6 +40,7 @@ CPP_SOURCES = [
 HIP_SOURCES = [
     "kernels/image_ops.hip",
     "kernels/svc_codec.hip",
+    "kernels/svc_encode.hip",
     "kernels/color.hip",
     "kernels/optflow.hip",
     "kernels/gemm_mfma.hip",

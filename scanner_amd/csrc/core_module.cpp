@@ -20,12 +20,18 @@
 #include "video/h264.h"
 #include "video/ingest.h"
 #include "video/mp4.h"
+#include "ops/jpeg_common.h"
 #include "ops/kernel.h"
 #include "ops/python_kernel.h"
 #include "video/svc.h"
 
 namespace py = pybind11;
 using namespace sca;
+
+namespace sca {
+// ops/image_encoder.cpp
+std::vector<u8> encode_png(const u8* pix, int h, int w, int c);
+}  // namespace sca
 
 namespace {
 
@@ -220,6 +226,7 @@ PYBIND11_MODULE(_core, m) {
   register_pose_op();
   register_color_gpu();
   register_image_encoder_op();
+  register_image_encoder_gpu();
   register_detector_op();
   register_files_source_sink();
 
@@ -821,6 +828,177 @@ PYBIND11_MODULE(_core, m) {
         py::arg("h"), py::arg("w"), py::arg("c"), py::arg("n"),
         py::arg("iters") = 1, py::arg("mode") = "gpu",
         py::arg("clip") = "smooth", py::arg("seed") = 0);
+  // ---- JPEG still-image encode (ops/jpeg_cpu.cpp, kernels/jpeg_encode.hip)
+  m.def("jpeg_restart_interval", []() { return kJpegRestartInterval; });
+  m.def("jpeg_size_bound", &jpeg_size_bound, py::arg("h"), py::arg("w"),
+        py::arg("c"));
+  // the oracle: one [H,W,C] u8 frame -> file bytes
+  m.def("jpeg_cpu_encode",
+        [](py::array_t<u8, py::array::c_style | py::array::forcecast> frame,
+           i32 quality) {
+          SCA_CHECK(frame.ndim() == 3, "frame must be [H,W,C]");
+          auto v = jpeg_encode_cpu(frame.data(), (i32)frame.shape(0),
+                                   (i32)frame.shape(1), (i32)frame.shape(2),
+                                   quality);
+          return py::bytes((const char*)v.data(), v.size());
+        },
+        py::arg("frame"), py::arg("quality") = 90);
+  // quantised coefficients, int16 [ncomp, by, bx, 64] in zig-zag order
+  m.def("jpeg_quantize_cpu",
+        [](py::array_t<u8, py::array::c_style | py::array::forcecast> frame,
+           i32 quality) {
+          SCA_CHECK(frame.ndim() == 3, "frame must be [H,W,C]");
+          i32 h = (i32)frame.shape(0), w = (i32)frame.shape(1),
+              c = (i32)frame.shape(2);
+          jpeg_check_args(h, w, c, quality);
+          JpegTables t;
+          jpeg_make_tables(c, quality, t);
+          JpegGeom g = jpeg_geom(h, w, c);
+          py::array_t<i16> out(
+              {(i64)c, (i64)g.mcus_y, (i64)g.mcus_x, (i64)64});
+          i16* o = out.mutable_data();
+          i16 zz[64];
+          for (i32 comp = 0; comp < c; ++comp)
+            for (u32 by = 0; by < g.mcus_y; ++by)
+              for (u32 bx = 0; bx < g.mcus_x; ++bx, o += 64) {
+                jpeg_block_coefs(frame.data(), h, w, c, bx, by, comp, t, zz);
+                std::memcpy(o, zz, sizeof(zz));
+              }
+          return out;
+        },
+        py::arg("frame"), py::arg("quality") = 90);
+  // [N,H,W,C] u8 frames are uploaded as ONE contiguous device buffer (frame
+  // i at i*H*W*C, so an odd frame size gives misaligned frames) and encoded
+  // in one call -> list of file bytes
+  m.def("jpeg_gpu_encode",
+        [](py::array_t<u8, py::array::c_style | py::array::forcecast> frames,
+           i32 quality) {
+          SCA_CHECK(have_gpu(), "jpeg_gpu_encode needs a GPU");
+          SCA_CHECK(frames.ndim() == 4, "frames must be [N,H,W,C]");
+          i64 n = frames.shape(0);
+          i32 h = (i32)frames.shape(1), w = (i32)frames.shape(2),
+              c = (i32)frames.shape(3);
+          jpeg_check_args(h, w, c, quality);
+          size_t fsize = (size_t)h * w * c;
+          DeviceHandle dev{DeviceType::GPU, 0};
+          py::list res;
+          if (n == 0) return res;
+          u8* d = new_buffer(dev, fsize * n);
+          std::vector<u8*> bufs;
+          std::vector<u64> sizes;
+          try {
+            memcpy_buffer(d, dev, frames.data(), CPU_DEVICE, fsize * n);
+            std::vector<const u8*> fp;
+            for (i64 i = 0; i < n; ++i) fp.push_back(d + (size_t)i * fsize);
+            jpeg_encode_gpu(fp, h, w, c, quality, dev, per_thread_hip_stream(),
+                            bufs, sizes);
+            for (size_t i = 0; i < bufs.size(); ++i) {
+              std::string host(sizes[i], '\0');
+              memcpy_buffer((u8*)host.data(), CPU_DEVICE, bufs[i], dev,
+                            sizes[i]);
+              res.append(py::bytes(host));
+            }
+          } catch (...) {
+            for (u8* b : bufs) delete_buffer(dev, b);
+            delete_buffer(dev, d);
+            throw;
+          }
+          for (u8* b : bufs) delete_buffer(dev, b);
+          delete_buffer(dev, d);
+          return res;
+        },
+        py::arg("frames"), py::arg("quality") = 90);
+  // Seconds for `iters` encodes of `batch` device-resident h*w*c frames,
+  // each ending with the files in host memory. mode "gpu": jpeg_encode_gpu,
+  // then D2H of the compressed bytes. mode "cpu": D2H of the raw frames,
+  // then jpeg_encode_cpu. mode "png": D2H of the raw frames, then the PNG
+  // writer (the only image path before the JPEG encoder). Also returns the
+  // bytes produced by one iteration. clip: "smooth" gradients or "noise".
+  m.def("jpeg_encode_bench",
+        [](i32 h, i32 w, i32 c, i32 quality, i64 batch, i32 iters,
+           const std::string& mode, const std::string& clip) {
+          SCA_CHECK(have_gpu(), "jpeg_encode_bench needs a GPU");
+          SCA_CHECK(mode == "gpu" || mode == "cpu" || mode == "png",
+                    "mode must be 'gpu', 'cpu' or 'png'");
+          SCA_CHECK(clip == "smooth" || clip == "noise",
+                    "clip must be 'smooth' or 'noise'");
+          jpeg_check_args(h, w, c, quality);
+          SCA_CHECK(batch > 0 && iters > 0, "empty benchmark");
+          size_t fsize = (size_t)h * w * c;
+          DeviceHandle dev{DeviceType::GPU, 0};
+          u8* d = new_block_buffer(dev, fsize * batch, 1);
+          double secs = 0;
+          u64 out_bytes = 0;
+          try {
+            {
+              std::vector<u8> host(fsize * batch);
+              u32 x = 2654435761u;
+              size_t p = 0;
+              for (i64 i = 0; i < batch; ++i)
+                for (i32 y = 0; y < h; ++y)
+                  for (i32 xx = 0; xx < w; ++xx)
+                    for (i32 ch = 0; ch < c; ++ch, ++p) {
+                      if (clip == "noise") {
+                        x ^= x << 13; x ^= x >> 17; x ^= x << 5;
+                        host[p] = (u8)(x >> 24);
+                      } else {
+                        i64 v = ch % 3 == 0   ? xx + i * 2
+                                : ch % 3 == 1 ? y + i
+                                              : (xx + y) / 2 + i * 3;
+                        host[p] = (u8)(v & 0xff);
+                      }
+                    }
+              memcpy_buffer(d, dev, host.data(), CPU_DEVICE, fsize * batch);
+            }
+            std::vector<const u8*> fp;
+            for (i64 i = 0; i < batch; ++i) fp.push_back(d + (size_t)i * fsize);
+            py::gil_scoped_release rel;
+            auto t0 = std::chrono::steady_clock::now();
+            for (i32 it = 0; it < iters; ++it) {
+              out_bytes = 0;
+              if (mode == "gpu") {
+                std::vector<u8*> bufs;
+                std::vector<u64> sizes;
+                jpeg_encode_gpu(fp, h, w, c, quality, dev,
+                                per_thread_hip_stream(), bufs, sizes);
+                std::vector<u8*> dst;
+                std::vector<const u8*> src(bufs.begin(), bufs.end());
+                std::vector<size_t> sz(sizes.begin(), sizes.end());
+                for (u64 s : sizes) {
+                  dst.push_back(new_buffer(CPU_DEVICE, s));
+                  out_bytes += s;
+                }
+                memcpy_vec(dst, CPU_DEVICE, src, dev, sz);
+                for (u8* b : dst) delete_buffer(CPU_DEVICE, b);
+                for (u8* b : bufs) delete_buffer(dev, b);
+              } else {
+                std::vector<u8*> dst;
+                std::vector<size_t> sz(batch, fsize);
+                for (i64 i = 0; i < batch; ++i)
+                  dst.push_back(new_buffer(CPU_DEVICE, fsize));
+                memcpy_vec(dst, CPU_DEVICE, fp, dev, sz);
+                for (i64 i = 0; i < batch; ++i) {
+                  auto v = mode == "cpu"
+                               ? jpeg_encode_cpu(dst[i], h, w, c, quality)
+                               : encode_png(dst[i], h, w, c);
+                  out_bytes += v.size();
+                  delete_buffer(CPU_DEVICE, dst[i]);
+                }
+              }
+            }
+            secs = std::chrono::duration<double>(
+                       std::chrono::steady_clock::now() - t0)
+                       .count();
+          } catch (...) {
+            delete_buffer(dev, d);
+            throw;
+          }
+          delete_buffer(dev, d);
+          return py::make_tuple(secs, out_bytes);
+        },
+        py::arg("h"), py::arg("w"), py::arg("c"), py::arg("quality") = 90,
+        py::arg("batch") = 8, py::arg("iters") = 1, py::arg("mode") = "gpu",
+        py::arg("clip") = "smooth");
   m.def("span_cache_clear", &span_cache_clear);
   m.def("span_cache_set_budget", &span_cache_set_budget);
   // engine memory accounting (device -1 = CPU)

@@ -1,8 +1,9 @@
-// ImageEncoder op: u8 frames -> PNG blobs (capability parity:
+// ImageEncoder op: u8 frames -> PNG or JPEG blobs (capability parity:
 // scanner/util/image_encoder.cpp, which registers an ImageEncoder op
-// backed by lodepng/OpenCV). Here: a from-scratch PNG writer over the
-// system zlib (deflate of filter-0 scanlines), supporting gray (1ch) and
-// RGB (3ch) u8 frames. CPU-only, like the reference.
+// backed by lodepng/OpenCV). PNG: a from-scratch writer over the system
+// zlib (deflate of filter-0 scanlines). JPEG: the baseline encoder of
+// jpeg_cpu.cpp. Both take gray (1ch) and RGB (3ch) u8 frames. This is the
+// CPU kernel; the GPU kernel (JPEG only) lives in kernels/jpeg_encode.hip.
 #include <zlib.h>
 
 #include <cstring>
@@ -10,6 +11,7 @@
 
 #include "../memory.h"
 #include "../msgpack.h"
+#include "jpeg_common.h"
 #include "kernel.h"
 
 namespace sca {
@@ -34,6 +36,9 @@ void put_chunk(std::vector<u8>& png, const char type[4], const u8* data,
   put_be32(png, crc);
 }
 
+}  // namespace
+
+// also timed by the jpeg_encode_bench binding
 std::vector<u8> encode_png(const u8* pix, int h, int w, int c) {
   SCA_CHECK(c == 1 || c == 3, "PNG encoder supports 1- or 3-channel u8");
   // filter byte 0 before every scanline
@@ -68,33 +73,43 @@ std::vector<u8> encode_png(const u8* pix, int h, int w, int c) {
   return png;
 }
 
+namespace {
+
 class ImageEncoderKernelCPU : public BatchedKernel {
  public:
   explicit ImageEncoderKernelCPU(const KernelConfig& cfg)
       : BatchedKernel(cfg) {
     auto a = mp::decode(cfg.args);
     format_ = a.get_str("format", "png");
-    SCA_CHECK(format_ == "png",
-              "ImageEncoder supports format=png (no OpenCV/libjpeg in "
-              "this build)");
+    SCA_CHECK(format_ == "png" || format_ == "jpg" || format_ == "jpeg",
+              "ImageEncoder supports format=png|jpg|jpeg, got '" + format_ +
+                  "'");
+    quality_ = (i32)a.get_int("quality", 90);
+    SCA_CHECK(format_ == "png" || (quality_ >= 1 && quality_ <= 100),
+              "ImageEncoder quality must be in 1..100, got " +
+                  std::to_string(quality_));
   }
   void execute_batch(const BatchedElements& in, BatchedElements& out) override {
     for (const Element& f : in[0]) {
       SCA_CHECK(f.is_frame && f.frame_info.type == FrameType::U8,
                 "ImageEncoder needs u8 frames");
-      auto png = encode_png(f.buffer, f.frame_info.shape[0],
-                            f.frame_info.shape[1], f.frame_info.shape[2]);
+      i32 h = f.frame_info.shape[0], w = f.frame_info.shape[1],
+          c = f.frame_info.shape[2];
+      auto blob = format_ == "png"
+                      ? encode_png(f.buffer, h, w, c)
+                      : jpeg_encode_cpu(f.buffer, h, w, c, quality_);
       Element e;
-      e.size = png.size();
+      e.size = blob.size();
       e.buffer = new_buffer(config_.device, e.size);
       e.device = config_.device;
-      std::memcpy(e.buffer, png.data(), png.size());
+      std::memcpy(e.buffer, blob.data(), blob.size());
       out[0].push_back(e);
     }
   }
 
  private:
   std::string format_;
+  i32 quality_;
 };
 
 }  // namespace

@@ -166,6 +166,7 @@ void register_optflow_gpu();
 void register_pose_op();
 void register_color_gpu();
 void register_image_encoder_op();
+void register_image_encoder_gpu();
 void register_detector_op();
 
 }  // namespace sca

@@ -26,6 +26,7 @@ CPP_SOURCES = [
     "csrc/ops/resnet50.cpp",
     "csrc/ops/pose.cpp",
     "csrc/ops/image_encoder.cpp",
+    "csrc/ops/jpeg_cpu.cpp",
     "csrc/ops/detector.cpp",
     "csrc/ops/files_source.cpp",
     "csrc/engine/table_io.cpp",
@@ -41,6 +42,7 @@ HIP_SOURCES = [
     "kernels/image_ops.hip",
     "kernels/svc_codec.hip",
     "kernels/svc_encode.hip",
+    "kernels/jpeg_encode.hip",
     "kernels/color.hip",
     "kernels/optflow.hip",
     "kernels/gemm_mfma.hip",

@@ -20,6 +20,7 @@
 #include "video/h264.h"
 #include "video/ingest.h"
 #include "video/mp4.h"
+#include "ops/image_decode.h"
 #include "ops/jpeg_common.h"
 #include "ops/kernel.h"
 #include "ops/python_kernel.h"
@@ -227,6 +228,8 @@ PYBIND11_MODULE(_core, m) {
   register_color_gpu();
   register_image_encoder_op();
   register_image_encoder_gpu();
+  register_image_decoder_op();
+  register_image_decoder_gpu();
   register_detector_op();
   register_files_source_sink();
 
@@ -999,6 +1002,180 @@ PYBIND11_MODULE(_core, m) {
         py::arg("h"), py::arg("w"), py::arg("c"), py::arg("quality") = 90,
         py::arg("batch") = 8, py::arg("iters") = 1, py::arg("mode") = "gpu",
         py::arg("clip") = "smooth");
+  // ---- still-image decode (ops/jpeg_decode_cpu.cpp, ops/png_decode.cpp,
+  // kernels/jpeg_decode.hip)
+  auto image_to_array = [](const DecodedImage& img) {
+    py::array_t<u8> a({(i64)img.h, (i64)img.w, (i64)img.c});
+    std::memcpy(a.mutable_data(), img.pixels.data(), img.pixels.size());
+    return a;
+  };
+  m.def("jpeg_decode_info", [](py::bytes blob) {
+    std::string s = blob;
+    JpegInfo in = jpeg_parse((const u8*)s.data(), s.size());
+    py::dict d;
+    d["h"] = in.g.h;
+    d["w"] = in.g.w;
+    d["c"] = in.g.nc;
+    d["hs"] = in.g.hs;
+    d["vs"] = in.g.vs;
+    d["mcus"] = in.g.nmcu;
+    d["restart_interval"] = in.restart_interval;
+    py::list segs;
+    for (auto& sg : in.segments)
+      segs.append(py::make_tuple(sg.begin, sg.end, sg.first_mcu,
+                                 sg.mcu_count));
+    d["segments"] = segs;
+    return d;
+  });
+  // the oracle: file bytes -> [H,W,C] u8
+  m.def("jpeg_cpu_decode", [image_to_array](py::bytes blob) {
+    std::string s = blob;
+    return image_to_array(jpeg_decode_cpu((const u8*)s.data(), s.size()));
+  });
+  m.def("png_cpu_decode", [image_to_array](py::bytes blob) {
+    std::string s = blob;
+    return image_to_array(png_decode((const u8*)s.data(), s.size()));
+  });
+  m.def("image_cpu_decode", [image_to_array](py::bytes blob) {
+    std::string s = blob;
+    return image_to_array(image_decode_cpu((const u8*)s.data(), s.size()));
+  });
+  // dequantised int32 blocks [N,64] (natural order; values are clamped to
+  // the decoder's coefficient limit) -> u8 samples [N,64]
+  m.def("jpeg_idct_blocks",
+        [](py::array_t<i32, py::array::c_style | py::array::forcecast> blocks) {
+          SCA_CHECK(blocks.ndim() == 2 && blocks.shape(1) == 64,
+                    "blocks must be [N,64]");
+          i64 n = blocks.shape(0);
+          py::array_t<u8> out({n, (i64)64});
+          const i32* src = blocks.data();
+          u8* dst = out.mutable_data();
+          for (i64 b = 0; b < n; ++b) {
+            i32 deq[64];
+            u8 pix[64];
+            for (int k = 0; k < 64; ++k) {
+              i32 v = src[b * 64 + k];
+              deq[k] = v < -kJpegCoefLimit  ? -kJpegCoefLimit
+                       : v > kJpegCoefLimit ? kJpegCoefLimit
+                                            : v;
+            }
+            jpeg_idct_block(deq, pix);
+            std::memcpy(dst + b * 64, pix, 64);
+          }
+          return out;
+        });
+  // One batch through jpeg_decode_gpu -> list of [H,W,C] u8 arrays, in
+  // order; with host_rows=True also the number of rows the CPU decoders
+  // handled (JPEG without DRI, PNG).
+  m.def("jpeg_gpu_decode",
+        [](const std::vector<py::bytes>& blobs, bool want_host_rows)
+            -> py::object {
+          SCA_CHECK(have_gpu(), "jpeg_gpu_decode needs a GPU");
+          DeviceHandle dev{DeviceType::GPU, 0};
+          std::vector<std::string> data(blobs.begin(), blobs.end());
+          std::vector<ImageBlob> ib;
+          std::vector<JpegInfo> infos(data.size());
+          for (size_t i = 0; i < data.size(); ++i) {
+            ib.push_back({(const u8*)data[i].data(), data[i].size()});
+            if (is_jpeg(ib[i].data, ib[i].size)) {
+              try {
+                infos[i] = jpeg_parse(ib[i].data, ib[i].size);
+              } catch (const ScannerError& err) {
+                throw ScannerError("ImageDecoder: row " + std::to_string(i) +
+                                   " of the batch: " + err.what());
+              }
+            }
+          }
+          std::vector<DeviceFrame> frames;
+          i64 host_rows = 0;
+          jpeg_decode_gpu(ib, infos, dev, per_thread_hip_stream(), frames,
+                          &host_rows);
+          py::list res;
+          try {
+            for (auto& f : frames) {
+              py::array_t<u8> a({(i64)f.h, (i64)f.w, (i64)f.c});
+              memcpy_buffer(a.mutable_data(), CPU_DEVICE, f.buffer, dev,
+                            (size_t)f.h * f.w * f.c);
+              res.append(a);
+            }
+          } catch (...) {
+            for (auto& f : frames) delete_buffer(dev, f.buffer);
+            throw;
+          }
+          for (auto& f : frames) delete_buffer(dev, f.buffer);
+          if (want_host_rows) return py::make_tuple(res, host_rows);
+          return std::move(res);
+        },
+        py::arg("blobs"), py::arg("host_rows") = false);
+  // Seconds of each of `iters` decodes of the batch, every one ending with
+  // the frames resident in HBM. mode "gpu": jpeg_parse + jpeg_decode_gpu
+  // (compressed H2D inside). mode "cpu": jpeg_decode_cpu on this thread,
+  // then H2D of the raw frames. mode "upload": the blobs are raw pixels
+  // already (another decoder's output); one host copy and the H2D.
+  m.def("jpeg_decode_bench",
+        [](const std::vector<py::bytes>& blobs, i32 iters,
+           const std::string& mode) {
+          SCA_CHECK(have_gpu(), "jpeg_decode_bench needs a GPU");
+          SCA_CHECK(mode == "gpu" || mode == "cpu" || mode == "upload",
+                    "mode must be 'gpu', 'cpu' or 'upload'");
+          SCA_CHECK(!blobs.empty() && iters > 0, "empty benchmark");
+          DeviceHandle dev{DeviceType::GPU, 0};
+          std::vector<std::string> data(blobs.begin(), blobs.end());
+          std::vector<double> secs;
+          py::gil_scoped_release rel;
+          for (i32 it = 0; it < iters; ++it) {
+            auto t0 = std::chrono::steady_clock::now();
+            if (mode == "gpu") {
+              std::vector<ImageBlob> ib;
+              std::vector<JpegInfo> infos(data.size());
+              for (size_t i = 0; i < data.size(); ++i) {
+                ib.push_back({(const u8*)data[i].data(), data[i].size()});
+                infos[i] = jpeg_parse(ib[i].data, ib[i].size);
+              }
+              std::vector<DeviceFrame> frames;
+              jpeg_decode_gpu(ib, infos, dev, per_thread_hip_stream(),
+                              frames);
+              secs.push_back(std::chrono::duration<double>(
+                                 std::chrono::steady_clock::now() - t0)
+                                 .count());
+              for (auto& f : frames) delete_buffer(dev, f.buffer);
+            } else {
+              std::vector<DecodedImage> imgs;
+              size_t total = 0;
+              for (auto& d : data) {
+                if (mode == "upload") {  // the blobs are decoded pixels
+                  imgs.emplace_back();
+                  imgs.back().pixels.assign(d.begin(), d.end());
+                } else {
+                  imgs.push_back(
+                      jpeg_decode_cpu((const u8*)d.data(), d.size()));
+                }
+                total += (imgs.back().pixels.size() + 255) / 256 * 256;
+              }
+              u8* block = new_block_buffer(dev, total, 1);
+              std::vector<u8*> dst;
+              std::vector<const u8*> src;
+              std::vector<size_t> sz;
+              size_t pos = 0;
+              for (auto& im : imgs) {
+                dst.push_back(block + pos);
+                src.push_back(im.pixels.data());
+                sz.push_back(im.pixels.size());
+                pos += (im.pixels.size() + 255) / 256 * 256;
+              }
+              memcpy_vec(dst, dev, src, CPU_DEVICE, sz);
+              secs.push_back(std::chrono::duration<double>(
+                                 std::chrono::steady_clock::now() - t0)
+                                 .count());
+              delete_buffer(dev, block);
+            }
+          }
+          return secs;
+        },
+        py::arg("blobs"), py::arg("iters") = 1, py::arg("mode") = "gpu");
+  // seconds the calling thread's last jpeg_decode_gpu waited in its stream
+  // synchronise (the rest of the call is host work: parse, pack, enqueue)
+  m.def("jpeg_decode_last_sync_seconds", &jpeg_decode_gpu_last_sync_seconds);
   m.def("span_cache_clear", &span_cache_clear);
   m.def("span_cache_set_budget", &span_cache_set_budget);
   // engine memory accounting (device -1 = CPU)

@@ -1046,6 +1046,8 @@ void LocalExecutor::process_task(Instance& inst, const TaskDesc& t,
         // ---- kernel op: advance [cursor, target) in batches ----
         BaseKernel* kernel = inst.kernels[i].get();
         DeviceHandle kdev = kernel->config().device;
+        const bool host_inputs =
+            kernel_registry().get(op.name, op.device).host_inputs;
         auto& out_maps = outs[i];
         auto rit = reads[i].end();  // re-looked-up per column below
 
@@ -1069,8 +1071,10 @@ void LocalExecutor::process_task(Instance& inst, const TaskDesc& t,
                 SCA_CHECK(pit != parent_map.end(),
                           "kernel input row missing for op '" + op.name +
                               "'");
-                bool copied;
-                Element e = element_to_device(pit->second, kdev, copied);
+                bool copied = false;
+                Element e = host_inputs
+                                ? pit->second
+                                : element_to_device(pit->second, kdev, copied);
                 if (copied) scratch.push_back(e);
                 input[c][r - bi].push_back(e);
               }

@@ -1,0 +1,87 @@
+// Still-image decode: baseline JPEG and 8-bit PNG files -> HWC u8 frames.
+// The CPU decoders (jpeg_decode_cpu.cpp, png_decode.cpp) are HIP-free and
+// define the pixels; kernels/jpeg_decode.hip reproduces the JPEG ones on the
+// GPU from the same arithmetic (jpeg_decode_common.h).
+//
+// Accepted JPEG: SOF0, or SOF1 at 8-bit precision; 1 component, or 3
+// components taken as YCbCr with luma sampling 1x1, 2x1 or 2x2 and chroma
+// 1x1; one interleaved scan; any restart interval. Accepted PNG: 8-bit
+// grey, RGB or RGBA (alpha dropped), not interlaced. Everything else is
+// rejected with a message that names the cause. No parser or decoder reads
+// outside the bytes it is given.
+#pragma once
+
+#include <string>
+#include <vector>
+
+#include "jpeg_decode_common.h"
+
+namespace sca {
+
+// One restart segment of the scan: bytes [begin, end) of the file (the RSTn
+// marker that follows is not included) and the MCUs it holds.
+struct JpegSegment {
+  u32 begin, end;
+  u32 first_mcu, mcu_count;
+};
+
+struct JpegInfo {
+  JpegDecGeom g{};
+  u32 restart_interval = 0;  // MCUs; 0 = the file has no DRI segment
+  u16 q[3][64];              // per component, natural order
+  JpegHuff dc[3], ac[3];     // per component
+  u8 zz2nat[64];
+  std::vector<JpegSegment> segments;
+};
+
+JpegInfo jpeg_parse(const u8* data, size_t size);
+
+struct DecodedImage {
+  i32 h = 0, w = 0, c = 0;
+  std::vector<u8> pixels;  // HWC
+};
+
+// The oracle: serial, from jpeg_decode_common.h.
+DecodedImage jpeg_decode_cpu(const u8* data, size_t size);
+// Decode of an already parsed file into h*w*c bytes at `out`.
+void jpeg_decode_cpu_into(const u8* data, const JpegInfo& info, u8* out);
+// Text of an entropy error, shared with the GPU decoder's report.
+std::string jpeg_entropy_error(u32 status, u32 segment);
+
+// IHDR only: the output shape (c is 1 or 3), after the same checks
+// png_decode makes on the header.
+void png_shape(const u8* data, size_t size, i32& h, i32& w, i32& c);
+DecodedImage png_decode(const u8* data, size_t size);
+
+bool is_jpeg(const u8* data, size_t size);
+bool is_png(const u8* data, size_t size);
+// Dispatch on the magic bytes.
+DecodedImage image_decode_cpu(const u8* data, size_t size);
+
+// ---- HIP decoder (kernels/jpeg_decode.hip) ----
+struct ImageBlob {
+  const u8* data;  // host memory
+  size_t size;
+};
+struct DeviceFrame {
+  u8* buffer = nullptr;  // HWC u8 on the device, release with delete_buffer
+  i32 h = 0, w = 0, c = 0;
+};
+// Decodes a batch of files (any mix of shapes, samplings and tables) into
+// device frames, in order. infos[i] is jpeg_parse of blobs[i] for a JPEG row
+// and is ignored for a PNG row. JPEG rows with a DRI segment are decoded on
+// the device, one lane per restart segment; JPEG rows without one and PNG
+// rows are decoded by the CPU decoders and uploaded (*host_rows counts
+// them). Everything is issued on `stream`, which is synchronised once, after
+// the per-file status words have been copied back; a corrupt row raises
+// ScannerError naming the row and no frame of the call survives. The frames
+// share one block buffer: release each with delete_buffer(dev, buffer).
+void jpeg_decode_gpu(const std::vector<ImageBlob>& blobs,
+                     const std::vector<JpegInfo>& infos, DeviceHandle dev,
+                     void* stream, std::vector<DeviceFrame>& out_frames,
+                     i64* host_rows = nullptr);
+// Seconds the calling thread's last jpeg_decode_gpu spent waiting in its
+// stream synchronise.
+double jpeg_decode_gpu_last_sync_seconds();
+
+}  // namespace sca

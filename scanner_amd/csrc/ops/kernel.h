@@ -118,6 +118,12 @@ struct KernelFactory {
   i32 preferred_batch = 1;
   // number of devices this kernel wants (reference .num_devices());
   i32 num_devices = 1;
+  // true: the executor hands this kernel its inputs where they live instead
+  // of copying each element to the kernel device first. For kernels that
+  // read their inputs on the host and do their own upload (GPU
+  // ImageDecoder: headers are parsed on the host, the entropy-coded bytes
+  // of a batch go up in one copy).
+  bool host_inputs = false;
   std::function<std::unique_ptr<BaseKernel>(const KernelConfig&)> make;
 };
 
@@ -167,6 +173,8 @@ void register_pose_op();
 void register_color_gpu();
 void register_image_encoder_op();
 void register_image_encoder_gpu();
+void register_image_decoder_op();
+void register_image_decoder_gpu();
 void register_detector_op();
 
 }  // namespace sca

@@ -1,0 +1,522 @@
+// GPU baseline JPEG decoder for gfx950: files in host memory become HWC u8
+// frames in HBM, byte-identical to jpeg_decode_cpu, so an image source moves
+// only compressed bytes over the host link. Formats and the shared integer
+// arithmetic: csrc/ops/image_decode.h, csrc/ops/jpeg_decode_common.h.
+//
+// A JPEG scan is one serial bit stream except at restart markers, where the
+// DC prediction and the bit alignment start afresh; so the unit of
+// parallelism is the restart segment. Files without a DRI segment (and PNG
+// files) are decoded by the CPU decoders and uploaded.
+//
+// Per batch (any mix of shapes, samplings and tables):
+//   host     parse every file; pack status words, one descriptor per file
+//            (geometry, quantisation and Huffman tables), one record per
+//            workgroup, one record per segment and the entropy-coded bytes
+//            into one pinned staging buffer -> one hipMemcpyAsync
+//   entropy  one lane per restart segment, 64 segments of ONE file per
+//            workgroup; the file's descriptor sits in LDS. A lane decodes a
+//            block into its private 64 x int16 slot of an LDS tile (the
+//            zig-zag scatter needs addressable storage), runs the IDCT on
+//            it from registers and stores 8 rows of 8 bytes to the padded
+//            component plane (grey: straight to the image). Coefficients
+//            never reach HBM. The lanes share no data after the descriptor
+//            load, so the loop has no barrier.
+//   colour   one lane per 4 output pixels: chroma upsampling and
+//            YCbCr -> RGB, 12 bytes stored as three dwords. Grey files skip
+//            it.
+//   status   one word per file, atomicMin of (segment << 4 | cause), read
+//            back with one D2H and the only stream synchronise of the call.
+//
+// Safety on hostile entropy data: every read is bounded by the segment
+// record (JpegBitReader), every coefficient write by the 64-entry slot
+// (jpeg_decode_block), every plane write by the MCU count of the geometry,
+// and the loops by MCU count x blocks per MCU x 64 symbols. A lane that
+// meets an error records it and stops; the host discards the image.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+
+#include "../csrc/memory.h"
+#include "../csrc/ops/image_decode.h"
+#include "../csrc/ops/kernel.h"
+
+namespace sca {
+
+namespace {
+
+#define JPEG_DEC_CHECK(expr)                                             \
+  do {                                                                   \
+    hipError_t _e = (expr);                                              \
+    if (_e != hipSuccess) {                                              \
+      throw ScannerError(std::string("HIP error in jpeg decode: ") +     \
+                         hipGetErrorString(_e));                         \
+    }                                                                    \
+  } while (0)
+
+constexpr u32 kLanes = 64;        // restart segments per workgroup
+constexpr u32 kSlotStride = 66;   // int16 per lane slot: 33 words, so lanes
+                                  // reading the same coefficient hit
+                                  // different banks
+constexpr u32 kColourThreads = 256;
+constexpr u32 kNoError = 0xffffffffu;
+
+struct JpegDecFile {
+  JpegDecGeom g;
+  u32 status_index;
+  u32 pad;
+  u64 plane_off[3];  // into the plane workspace; unused for grey
+  u8* out;           // HWC u8
+  u16 q[3][64];
+  u8 zz2nat[64];
+  JpegHuff dc[3], ac[3];
+};
+static_assert(sizeof(JpegDecFile) % 8 == 0, "descriptors are copied as words");
+
+struct JpegDecGroup {
+  u32 file;
+  u32 seg0;        // first segment record of the workgroup
+  u32 nseg;        // lanes in use
+  u32 file_seg0;   // index of that segment inside its file
+};
+struct JpegDecSeg {
+  u32 begin, end;  // into the packed entropy bytes
+  u32 first_mcu, mcu_count;
+};
+
+struct JpegDecArgs {
+  const JpegDecFile* files;
+  const JpegDecGroup* groups;
+  const JpegDecSeg* segs;
+  const u8* entropy;
+  u8* planes;
+  u32* status;
+  u32 nfiles;
+};
+
+__global__ void __launch_bounds__(kLanes) jpeg_entropy_idct_kernel(
+    JpegDecArgs a) {
+  __shared__ JpegDecFile f;
+  __shared__ i16 tile[kLanes * kSlotStride];
+  const JpegDecGroup grp = a.groups[blockIdx.x];
+  u32 lane = threadIdx.x;
+  {
+    const u32* src = reinterpret_cast<const u32*>(a.files + grp.file);
+    u32* dst = reinterpret_cast<u32*>(&f);
+    for (u32 i = lane; i < sizeof(JpegDecFile) / 4; i += kLanes) dst[i] = src[i];
+  }
+  __syncthreads();
+  if (lane >= grp.nseg) return;
+  const JpegDecGeom& g = f.g;
+  const JpegDecSeg seg = a.segs[grp.seg0 + lane];
+  // the host builds the records from the same geometry; the clamp makes
+  // every plane write below in range whatever they hold
+  u32 m0 = min(seg.first_mcu, g.nmcu);
+  u32 m1 = m0 + min(seg.mcu_count, g.nmcu - m0);
+
+  JpegBitReader br;
+  jpeg_bits_init(br, a.entropy, seg.begin, seg.end);
+  i32 pred[3] = {0, 0, 0};
+  i16* slot = tile + lane * kSlotStride;
+  u32* slot32 = reinterpret_cast<u32*>(slot);
+
+  for (u32 m = m0; m < m1; ++m) {
+    for (u32 b = 0; b < g.blocks_per_mcu; ++b) {
+      u32 comp, px, py;
+      jpeg_block_pos(g, m, b, comp, px, py);
+#pragma unroll
+      for (u32 i = 0; i < 32; ++i) slot32[i] = 0;
+      i32 p = comp == 0 ? pred[0] : comp == 1 ? pred[1] : pred[2];
+      u32 st = jpeg_decode_block(br, f.dc[comp], f.ac[comp], f.zz2nat, p, slot);
+      if (comp == 0) pred[0] = p; else if (comp == 1) pred[1] = p; else pred[2] = p;
+      if (st != kJpegBlockOk) {
+        atomicMin(&a.status[f.status_index], (grp.file_seg0 + lane) << 4 | st);
+        return;
+      }
+      i32 deq[64];
+      const u16* q = f.q[comp];
+#pragma unroll
+      for (int k = 0; k < 64; ++k) deq[k] = jpeg_dequant(slot[k], q[k]);
+      u8 pix[64];
+      jpeg_idct_block(deq, pix);
+      if (g.nc == 1) {
+        // the image itself: only the part of the block inside it
+        u8* dst = f.out;
+#pragma unroll
+        for (u32 y = 0; y < 8; ++y) {
+          if (py + y >= (u32)g.h) break;
+#pragma unroll
+          for (u32 x = 0; x < 8; ++x) {
+            if (px + x < (u32)g.w)
+              dst[(u64)(py + y) * (u32)g.w + px + x] = pix[y * 8 + x];
+          }
+        }
+      } else {
+        u32 stride = comp == 0 ? g.y_stride : g.c_stride;
+        u8* dst = a.planes + f.plane_off[comp] + (u64)py * stride + px;
+#pragma unroll
+        for (u32 y = 0; y < 8; ++y) {
+          uint2 v;
+          v.x = pix[y * 8] | pix[y * 8 + 1] << 8 | pix[y * 8 + 2] << 16 |
+                (u32)pix[y * 8 + 3] << 24;
+          v.y = pix[y * 8 + 4] | pix[y * 8 + 5] << 8 | pix[y * 8 + 6] << 16 |
+                (u32)pix[y * 8 + 7] << 24;
+          *reinterpret_cast<uint2*>(dst + (u64)y * stride) = v;
+        }
+      }
+    }
+  }
+}
+
+// grid (pixel groups of the largest file, files); a lane owns pixels
+// [4t, 4t + 4) of the flattened image, i.e. bytes [12t, 12t + 12)
+__global__ void __launch_bounds__(kColourThreads) jpeg_colour_kernel(
+    JpegDecArgs a) {
+  const JpegDecFile& f = a.files[blockIdx.y];
+  const JpegDecGeom g = f.g;
+  if (g.nc != 3) return;
+  u64 npix = (u64)g.h * g.w;
+  u64 p0 = ((u64)blockIdx.x * kColourThreads + threadIdx.x) * 4;
+  if (p0 >= npix) return;
+  const u8* yp = a.planes + f.plane_off[0];
+  const u8* cbp = a.planes + f.plane_off[1];
+  const u8* crp = a.planes + f.plane_off[2];
+  u8 rgb[12];
+  u32 n = (u32)min((u64)4, npix - p0);
+  u32 y = (u32)(p0 / (u32)g.w), x = (u32)(p0 % (u32)g.w);
+#pragma unroll
+  for (u32 i = 0; i < 4; ++i) {
+    if (i < n) {
+      jpeg_pixel_rgb(g, yp, cbp, crp, x, y, rgb + 3 * i);
+      if (++x == (u32)g.w) {
+        x = 0;
+        ++y;
+      }
+    } else {
+      rgb[3 * i] = rgb[3 * i + 1] = rgb[3 * i + 2] = 0;
+    }
+  }
+  u8* dst = f.out + p0 * 3;  // out is 256-byte aligned, p0 * 3 = 12 t
+  if (n == 4) {
+    u32* d4 = reinterpret_cast<u32*>(dst);
+#pragma unroll
+    for (u32 k = 0; k < 3; ++k)
+      d4[k] = rgb[4 * k] | rgb[4 * k + 1] << 8 | rgb[4 * k + 2] << 16 |
+              (u32)rgb[4 * k + 3] << 24;
+  } else {
+    for (u32 k = 0; k < 3 * n; ++k) dst[k] = rgb[k];
+  }
+}
+
+u64 align_up(u64 x, u64 a) { return (x + a - 1) / a * a; }
+
+thread_local double t_last_sync = 0;
+
+}  // namespace
+
+double jpeg_decode_gpu_last_sync_seconds() { return t_last_sync; }
+
+void jpeg_decode_gpu(const std::vector<ImageBlob>& blobs,
+                     const std::vector<JpegInfo>& infos, DeviceHandle dev,
+                     void* stream, std::vector<DeviceFrame>& out_frames,
+                     i64* host_rows) {
+  SCA_CHECK(dev.is_gpu(), "jpeg_decode_gpu needs a GPU device");
+  SCA_CHECK(infos.size() == blobs.size(), "one JpegInfo per blob");
+  size_t n = blobs.size();
+  out_frames.assign(n, DeviceFrame{});
+  if (host_rows) *host_rows = 0;
+  if (n == 0) return;
+  JPEG_DEC_CHECK(hipSetDevice(dev.id));
+  hipStream_t s = (hipStream_t)stream;
+
+  // ---- classify, decode the host rows, lay out the outputs ----
+  std::vector<int> kind(n, 0);  // 0 null, 1 device, 2 host
+  std::vector<DecodedImage> host_img(n);
+  std::vector<u64> out_off(n, 0);
+  u64 out_total = 0, host_pix_total = 0;
+  i32 live = 0;
+  size_t ndev = 0;
+  for (size_t i = 0; i < n; ++i) {
+    if (!blobs[i].data) continue;
+    DeviceFrame& fr = out_frames[i];
+    if (is_jpeg(blobs[i].data, blobs[i].size) &&
+        infos[i].restart_interval != 0) {
+      kind[i] = 1;
+      ++ndev;
+      fr.h = infos[i].g.h;
+      fr.w = infos[i].g.w;
+      fr.c = infos[i].g.nc;
+    } else {
+      kind[i] = 2;
+      try {
+        if (is_jpeg(blobs[i].data, blobs[i].size)) {
+          host_img[i].h = infos[i].g.h;
+          host_img[i].w = infos[i].g.w;
+          host_img[i].c = infos[i].g.nc;
+          host_img[i].pixels.resize((size_t)infos[i].g.h * infos[i].g.w *
+                                    infos[i].g.nc);
+          jpeg_decode_cpu_into(blobs[i].data, infos[i],
+                               host_img[i].pixels.data());
+        } else {
+          host_img[i] = image_decode_cpu(blobs[i].data, blobs[i].size);
+        }
+      } catch (const ScannerError& err) {
+        throw ScannerError("ImageDecoder: row " + std::to_string(i) +
+                           " of the batch: " + err.what());
+      }
+      fr.h = host_img[i].h;
+      fr.w = host_img[i].w;
+      fr.c = host_img[i].c;
+      host_pix_total += align_up(host_img[i].pixels.size(), 256);
+      if (host_rows) ++*host_rows;
+    }
+    out_off[i] = out_total;
+    out_total += align_up((u64)fr.h * fr.w * fr.c, 256);
+    ++live;
+  }
+  if (live == 0) return;
+
+  // ---- staging layout: status | files | groups | segments | entropy |
+  // (host only) pixels of the host rows ----
+  size_t ngroups = 0, nsegs = 0;
+  u64 entropy_total = 0, planes_total = 0;
+  for (size_t i = 0; i < n; ++i) {
+    if (kind[i] != 1) continue;
+    const JpegInfo& in = infos[i];
+    nsegs += in.segments.size();
+    ngroups += (in.segments.size() + kLanes - 1) / kLanes;
+    entropy_total +=
+        align_up(in.segments.back().end - in.segments.front().begin, 16);
+    if (in.g.nc == 3)
+      planes_total += align_up((u64)in.g.y_stride * in.g.y_rows, 256) +
+                      2 * align_up((u64)in.g.c_stride * in.g.c_rows, 256);
+  }
+  u64 status_off = 0;
+  u64 files_off = align_up(status_off + 4 * ndev, 256);
+  u64 groups_off = align_up(files_off + sizeof(JpegDecFile) * ndev, 256);
+  u64 segs_off = align_up(groups_off + sizeof(JpegDecGroup) * ngroups, 256);
+  u64 entropy_off = align_up(segs_off + sizeof(JpegDecSeg) * nsegs, 256);
+  u64 upload = align_up(entropy_off + entropy_total, 256);
+  u64 host_pix_off = upload;
+  u64 status_back_off = host_pix_off + host_pix_total;
+  u64 staging_size = status_back_off + align_up(4 * ndev, 256) + 256;
+  SCA_CHECK(upload < (1ull << 32), "jpeg decode: batch of 4 GiB or more");
+
+  u8* out_block = nullptr;
+  u8* staging = nullptr;
+  u8* ws = nullptr;  // device: the uploaded part, then the planes
+  auto release = [&](bool outputs_too) {
+    if (staging) delete_buffer(CPU_DEVICE, staging);
+    if (ws) delete_buffer(dev, ws);
+    staging = ws = nullptr;
+    if (outputs_too && out_block) {
+      for (i32 k = 0; k < live; ++k) delete_buffer(dev, out_block);
+      out_block = nullptr;
+      out_frames.assign(n, DeviceFrame{});
+    }
+  };
+  try {
+    out_block = new_block_buffer(dev, out_total, live);
+    staging = new_buffer(CPU_DEVICE, staging_size);
+    if (ndev) ws = new_buffer(dev, upload + planes_total);
+    for (size_t i = 0; i < n; ++i)
+      if (kind[i]) out_frames[i].buffer = out_block + out_off[i];
+
+    u32 max_colour_blocks = 0;
+    if (ndev) {
+      u32* status = reinterpret_cast<u32*>(staging + status_off);
+      auto* files = reinterpret_cast<JpegDecFile*>(staging + files_off);
+      auto* groups = reinterpret_cast<JpegDecGroup*>(staging + groups_off);
+      auto* segs = reinterpret_cast<JpegDecSeg*>(staging + segs_off);
+      u8* entropy = staging + entropy_off;
+      u32 fi = 0, gi = 0, si = 0;
+      u64 epos = 0, ppos = 0;
+      for (size_t i = 0; i < n; ++i) {
+        if (kind[i] != 1) continue;
+        const JpegInfo& in = infos[i];
+        status[fi] = kNoError;
+        JpegDecFile& f = files[fi];
+        std::memset(&f, 0, sizeof(f));
+        f.g = in.g;
+        f.status_index = fi;
+        f.out = out_frames[i].buffer;
+        if (in.g.nc == 3) {
+          u64 ysz = align_up((u64)in.g.y_stride * in.g.y_rows, 256);
+          u64 csz = align_up((u64)in.g.c_stride * in.g.c_rows, 256);
+          f.plane_off[0] = ppos;
+          f.plane_off[1] = ppos + ysz;
+          f.plane_off[2] = ppos + ysz + csz;
+          ppos += ysz + 2 * csz;
+          u64 groups4 = ((u64)in.g.h * in.g.w + 3) / 4;
+          max_colour_blocks = std::max<u32>(
+              max_colour_blocks,
+              (u32)((groups4 + kColourThreads - 1) / kColourThreads));
+        }
+        std::memcpy(f.q, in.q, sizeof(f.q));
+        std::memcpy(f.zz2nat, in.zz2nat, sizeof(f.zz2nat));
+        for (int c = 0; c < 3; ++c) {
+          f.dc[c] = in.dc[c];
+          f.ac[c] = in.ac[c];
+        }
+        u32 base = in.segments.front().begin;
+        u32 len = in.segments.back().end - base;
+        std::memcpy(entropy + epos, blobs[i].data + base, len);
+        u32 nseg = (u32)in.segments.size();
+        for (u32 k = 0; k < nseg; k += kLanes)
+          groups[gi++] = {fi, si + k, std::min(kLanes, nseg - k), k};
+        for (const JpegSegment& sg : in.segments)
+          segs[si++] = {(u32)(epos + sg.begin - base),
+                        (u32)(epos + sg.end - base), sg.first_mcu,
+                        sg.mcu_count};
+        epos += align_up(len, 16);
+        ++fi;
+      }
+      JPEG_DEC_CHECK(
+          hipMemcpyAsync(ws, staging, upload, hipMemcpyHostToDevice, s));
+      JpegDecArgs a{};
+      a.status = reinterpret_cast<u32*>(ws + status_off);
+      a.files = reinterpret_cast<const JpegDecFile*>(ws + files_off);
+      a.groups = reinterpret_cast<const JpegDecGroup*>(ws + groups_off);
+      a.segs = reinterpret_cast<const JpegDecSeg*>(ws + segs_off);
+      a.entropy = ws + entropy_off;
+      a.planes = ws + upload;
+      a.nfiles = (u32)ndev;
+      jpeg_entropy_idct_kernel<<<(u32)ngroups, kLanes, 0, s>>>(a);
+      JPEG_DEC_CHECK(hipGetLastError());
+      if (max_colour_blocks) {
+        jpeg_colour_kernel<<<dim3(max_colour_blocks, (u32)ndev),
+                             kColourThreads, 0, s>>>(a);
+        JPEG_DEC_CHECK(hipGetLastError());
+      }
+      JPEG_DEC_CHECK(hipMemcpyAsync(staging + status_back_off,
+                                    ws + status_off, 4 * ndev,
+                                    hipMemcpyDeviceToHost, s));
+    }
+    // host rows: pixels through the pinned staging
+    u64 hpos = host_pix_off;
+    for (size_t i = 0; i < n; ++i) {
+      if (kind[i] != 2) continue;
+      size_t sz = host_img[i].pixels.size();
+      std::memcpy(staging + hpos, host_img[i].pixels.data(), sz);
+      JPEG_DEC_CHECK(hipMemcpyAsync(out_frames[i].buffer, staging + hpos, sz,
+                                    hipMemcpyHostToDevice, s));
+      hpos += align_up(sz, 256);
+    }
+    auto sync0 = std::chrono::steady_clock::now();
+    JPEG_DEC_CHECK(hipStreamSynchronize(s));  // the only one
+    t_last_sync = std::chrono::duration<double>(
+                      std::chrono::steady_clock::now() - sync0)
+                      .count();
+    if (ndev) {
+      const u32* back =
+          reinterpret_cast<const u32*>(staging + status_back_off);
+      u32 fi = 0;
+      for (size_t i = 0; i < n; ++i) {
+        if (kind[i] != 1) continue;
+        u32 st = back[fi++];
+        if (st != kNoError)
+          throw ScannerError("ImageDecoder: row " + std::to_string(i) +
+                             " of the batch: check failed: " +
+                             jpeg_entropy_error(st & 15u, st >> 4));
+      }
+    }
+  } catch (...) {
+    (void)hipStreamSynchronize(s);
+    release(true);
+    throw;
+  }
+  release(false);
+}
+
+namespace {
+
+// ImageDecoder on the GPU. Registered with host_inputs: the files stay where
+// the executor found them; this kernel parses them on the host and uploads
+// the entropy-coded bytes of the whole batch at once.
+class ImageDecoderKernelGPU : public BatchedKernel {
+ public:
+  using BatchedKernel::BatchedKernel;
+
+  void execute_batch(const BatchedElements& in, BatchedElements& out) override {
+    const ElementVector& col = in[0];
+    size_t n = col.size();
+    out[0].resize(n);
+    std::vector<ImageBlob> blobs(n, ImageBlob{nullptr, 0});
+    std::vector<JpegInfo> infos(n);
+    std::vector<u8*> host_copies;
+    std::vector<DeviceFrame> frames;
+    i64 host_rows = 0, live = 0;
+    try {
+      for (size_t i = 0; i < n; ++i) {
+        const Element& b = col[i];
+        if (b.is_null) continue;
+        SCA_CHECK(!b.is_frame, "ImageDecoder needs a bytes input");
+        const u8* p = b.buffer;
+        if (b.device.is_gpu()) {
+          // e.g. straight from a GPU ImageEncoder: compressed bytes are
+          // small, bring them to the host
+          u8* h = new_buffer(CPU_DEVICE, std::max<size_t>(b.size, 1));
+          host_copies.push_back(h);
+          memcpy_buffer(h, CPU_DEVICE, b.buffer, b.device, b.size);
+          p = h;
+        }
+        blobs[i] = {p, b.size};
+        ++live;
+        if (is_jpeg(p, b.size)) {
+          try {
+            infos[i] = jpeg_parse(p, b.size);
+          } catch (const ScannerError& err) {
+            throw ScannerError("ImageDecoder: row " + std::to_string(i) +
+                               " of the batch: " + err.what());
+          }
+        }
+      }
+      void* stream =
+          config_.hip_stream ? config_.hip_stream : per_thread_hip_stream();
+      jpeg_decode_gpu(blobs, infos, config_.device, stream, frames,
+                      &host_rows);
+    } catch (...) {
+      for (u8* h : host_copies) delete_buffer(CPU_DEVICE, h);
+      throw;
+    }
+    for (u8* h : host_copies) delete_buffer(CPU_DEVICE, h);
+    for (size_t i = 0; i < n; ++i) {
+      Element& e = out[0][i];
+      if (col[i].is_null) {
+        e.is_null = true;
+        continue;
+      }
+      e.is_frame = true;
+      e.frame_info.shape[0] = frames[i].h;
+      e.frame_info.shape[1] = frames[i].w;
+      e.frame_info.shape[2] = frames[i].c;
+      e.frame_info.type = FrameType::U8;
+      e.size = (size_t)frames[i].h * frames[i].w * frames[i].c;
+      e.buffer = frames[i].buffer;
+      e.device = config_.device;
+    }
+    if (config_.profiler) {
+      config_.profiler->increment("jpeg_gpu_decode_frames", live - host_rows);
+      config_.profiler->increment("image_decode_host_rows", host_rows);
+    }
+  }
+};
+
+}  // namespace
+
+void register_image_decoder_gpu() {
+  static bool done = false;
+  if (done) return;
+  done = true;
+  KernelFactory f;
+  f.op_name = "ImageDecoder";
+  f.device_type = DeviceType::GPU;
+  f.preferred_batch = 8;
+  f.host_inputs = true;
+  f.make = [](const KernelConfig& c) -> std::unique_ptr<BaseKernel> {
+    return std::make_unique<ImageDecoderKernelGPU>(c);
+  };
+  kernel_registry().add(f);
+}
+
+}  // namespace sca

@@ -1,0 +1,134 @@
+#!/usr/bin/env python3
+"""Still-image source A/B: the GPU JPEG decoder against the host paths.
+
+_core.jpeg_decode_bench on batches of 8 1080p files in host memory, each
+timed call ending with the decoded frames resident in HBM:
+
+  gpu     jpeg_parse + jpeg_decode_gpu (compressed H2D inside)
+  cpu     jpeg_decode_cpu on one core + H2D of the raw frames (the same
+          pixels as the gpu side)
+  pillow  Pillow decode + H2D of the raw frames (informational: a different
+          decoder)
+
+Files: our encoder at quality 90 ("smooth" and "noise", restart interval 32)
+and Pillow 4:2:0 with a restart marker per MCU row. The sides alternate in
+one process after a warm-up; each is reported as seconds per batch, median
+and spread (min..max) over --reps timed calls. Prints one JSON line per
+result and, with --md, appends a markdown table. Needs a GPU: there is no
+CPU fallback for a timing.
+"""
+import argparse
+import io
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from scanner_amd import _core  # noqa: E402
+
+
+def frames(clip, n, h=1080, w=1920):
+    yy, xx = np.mgrid[0:h, 0:w]
+    out = []
+    for i in range(n):
+        if clip == "noise":
+            f = np.random.RandomState(i).randint(0, 256, (h, w, 3))
+        else:
+            f = np.stack([(xx + 2 * i) % 256, (yy + i) % 256,
+                          ((xx + yy) // 2 + 3 * i) % 256], -1)
+        out.append(np.ascontiguousarray(f.astype(np.uint8)))
+    return out
+
+
+def pillow_side(blobs):
+    from PIL import Image
+    t0 = time.perf_counter()
+    raw = [np.asarray(Image.open(io.BytesIO(b))).tobytes() for b in blobs]
+    dt = time.perf_counter() - t0
+    return dt + _core.jpeg_decode_bench(raw, 1, "upload")[0]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--quality", type=int, default=90)
+    ap.add_argument("--md", help="append a markdown table to this file")
+    args = ap.parse_args()
+    if args.reps < 5:
+        ap.error("--reps must be >= 5")
+    if not _core.have_gpu():
+        sys.exit("bench_jpeg_decode needs a GPU")
+    from PIL import Image
+    _core.init_memory(4 << 30, 8 << 30, [0])
+    sets = {}
+    for clip in ("smooth", "noise"):
+        sets["ours_" + clip] = [_core.jpeg_cpu_encode(f, args.quality)
+                                for f in frames(clip, args.batch)]
+    pil = []
+    for f in frames("smooth", args.batch):
+        buf = io.BytesIO()
+        Image.fromarray(f).save(buf, "JPEG", quality=args.quality,
+                                subsampling=2, restart_marker_rows=1)
+        pil.append(buf.getvalue())
+    sets["pillow420_rows1_smooth"] = pil
+
+    rows = []
+    sync = {}  # per gpu mode: seconds waited in the call's synchronise
+    modes = ("gpu", "cpu", "pillow")
+
+    def run(mode, blobs):
+        if mode == "pillow":
+            return pillow_side(blobs)
+        s = _core.jpeg_decode_bench(blobs, 1, mode)[0]
+        if mode == "gpu":
+            sync[mode].append(_core.jpeg_decode_last_sync_seconds())
+        return s
+
+    for name, blobs in sets.items():
+        secs = {m: [] for m in modes}
+        sync.clear()
+        sync.update({m: [] for m in modes})
+        for m in modes:  # warm-up, every side
+            run(m, blobs)
+        for _ in range(args.reps):
+            for m in modes:
+                secs[m].append(run(m, blobs))
+        info = _core.jpeg_decode_info(blobs[0])
+        for m in modes:
+            med = statistics.median(secs[m])
+            r = {"files": name, "mode": m, "batch": args.batch,
+                 "reps": args.reps, "quality": args.quality,
+                 "segments_per_file": len(info["segments"]),
+                 "bytes_per_file": sum(map(len, blobs)) // len(blobs),
+                 "seconds": {"median": med, "min": min(secs[m]),
+                             "max": max(secs[m])},
+                 "frames_per_s": args.batch / med}
+            if sync[m]:  # warm-up call included; the median ignores it
+                r["sync_wait_seconds_median"] = statistics.median(sync[m])
+            rows.append(r)
+            print(json.dumps(r), flush=True)
+    _core.destroy_memory()
+    if args.md:
+        with open(args.md, "a") as f:
+            f.write("| files | side | median ms/batch | min..max ms | frames/s "
+                    "| segments/file | bytes/file | sync wait ms |\n"
+                    "|---|---|---|---|---|---|---|---|\n")
+            for r in rows:
+                s = {k: v * 1e3 for k, v in r["seconds"].items()}
+                f.write(f"| {r['files']} | {r['mode']} | {s['median']:.3f} | "
+                        f"{s['min']:.3f}..{s['max']:.3f} | "
+                        f"{r['frames_per_s']:.1f} | {r['segments_per_file']} "
+                        f"| {r['bytes_per_file']} | "
+                        + (f"{r['sync_wait_seconds_median'] * 1e3:.3f}"
+                           if "sync_wait_seconds_median" in r else "")
+                        + " |\n")
+
+
+if __name__ == "__main__":
+    main()

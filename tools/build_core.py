@@ -27,6 +27,9 @@ CPP_SOURCES = [
     "csrc/ops/pose.cpp",
     "csrc/ops/image_encoder.cpp",
     "csrc/ops/jpeg_cpu.cpp",
+    "csrc/ops/jpeg_decode_cpu.cpp",
+    "csrc/ops/png_decode.cpp",
+    "csrc/ops/image_decoder.cpp",
     "csrc/ops/detector.cpp",
     "csrc/ops/files_source.cpp",
     "csrc/engine/table_io.cpp",
@@ -43,6 +46,7 @@ HIP_SOURCES = [
     "kernels/svc_codec.hip",
     "kernels/svc_encode.hip",
     "kernels/jpeg_encode.hip",
+    "kernels/jpeg_decode.hip",
     "kernels/color.hip",
     "kernels/optflow.hip",
     "kernels/gemm_mfma.hip",

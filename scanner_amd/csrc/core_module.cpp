@@ -1216,6 +1216,179 @@ PYBIND11_MODULE(_core, m) {
   m.def("has_kernel", [](const std::string& op, i32 device) {
     return kernel_registry().has(op, (DeviceType)device);
   });
+  // One registered kernel, one execute() call, on inputs the caller shapes
+  // (tests/test_image_ops_*.py). `frames` are equal-shape u8 HWC arrays, or
+  // f32 H x W x 2 flow arrays. packed: all frames end to end in ONE block
+  // buffer without padding, so odd frame sizes sit at odd addresses as
+  // decoded frames do; otherwise one allocation per frame. Row i sees the
+  // elements i + stencil[j] (the same Element for every row that names it),
+  // so n + max(stencil) frames make n rows. Returns column 0 per row: frames
+  // as arrays shaped by their frame_info, blobs as bytes. With then_op, a
+  // second kernel runs on those outputs without leaving the device and the
+  // result is (first outputs, second outputs).
+  m.def(
+      "op_kernel_test",
+      [](const std::string& op, i32 device_type, const py::bytes& args_b,
+         const std::vector<py::array>& frames, const std::vector<i32>& stencil,
+         bool packed, const std::string& then_op,
+         const py::bytes& then_args_b) -> py::object {
+        SCA_CHECK(device_type == 0 || device_type == 1,
+                  "op_kernel_test: bad device type");
+        const bool gpu = device_type == (i32)DeviceType::GPU;
+        SCA_CHECK(!gpu || have_gpu(), "op_kernel_test needs a GPU");
+        const DeviceHandle dev = gpu ? kTestDev : CPU_DEVICE;
+        SCA_CHECK(!frames.empty(), "op_kernel_test: no frames");
+        SCA_CHECK(!stencil.empty() && stencil[0] == 0,
+                  "op_kernel_test: stencil must start at 0");
+        i32 reach = 0;
+        for (i32 s : stencil) {
+          SCA_CHECK(s >= 0, "op_kernel_test: negative stencil offset");
+          reach = std::max(reach, s);
+        }
+        SCA_CHECK((size_t)reach < frames.size(),
+                  "op_kernel_test: fewer frames than the stencil spans");
+        const size_t nrows = frames.size() - reach;
+
+        // host side: contiguous copies, one geometry
+        const bool is_f32 = py::isinstance<py::array_t<float>>(frames[0]);
+        SCA_CHECK(is_f32 || py::isinstance<py::array_t<u8>>(frames[0]),
+                  "op_kernel_test: frames must be uint8 or float32");
+        SCA_CHECK(frames[0].ndim() == 3, "op_kernel_test: frames must be 3-D");
+        FrameInfo fi;
+        for (int d = 0; d < 3; ++d) fi.shape[d] = (i32)frames[0].shape(d);
+        fi.type = is_f32 ? FrameType::F32 : FrameType::U8;
+        const size_t fbytes = fi.size();
+        std::vector<py::array> host;
+        for (const py::array& a : frames) {
+          SCA_CHECK((is_f32 ? py::isinstance<py::array_t<float>>(a)
+                            : py::isinstance<py::array_t<u8>>(a)) &&
+                        a.ndim() == 3 &&
+                        a.shape(0) == fi.shape[0] &&
+                        a.shape(1) == fi.shape[1] && a.shape(2) == fi.shape[2],
+                    "op_kernel_test: frames differ in shape or type");
+          host.push_back(py::array::ensure(a, py::array::c_style));
+          SCA_CHECK(host.back() && (size_t)host.back().nbytes() == fbytes,
+                    "op_kernel_test: frame is not contiguous");
+        }
+
+        // Everything allocated here or by the kernel is released on every
+        // way out, a rejected input included.
+        struct Owned {
+          std::vector<Element> elems;
+          ~Owned() {
+            for (Element& e : elems)
+              if (e.buffer) delete_buffer(e.device, e.buffer);
+          }
+        } inputs, outputs;
+        u8* block = nullptr;
+        if (packed)
+          block = new_block_buffer(dev, fbytes * host.size(),
+                                   (i32)host.size());
+        for (size_t i = 0; i < host.size(); ++i) {
+          Element e;
+          e.is_frame = true;
+          e.frame_info = fi;
+          e.size = fbytes;
+          e.device = dev;
+          e.index = (i64)i;
+          e.buffer = packed ? block + i * fbytes : new_buffer(dev, fbytes);
+          inputs.elems.push_back(e);
+        }
+        for (size_t i = 0; i < host.size(); ++i)
+          memcpy_buffer(inputs.elems[i].buffer, dev,
+                        (const u8*)host[i].data(), CPU_DEVICE, fbytes);
+
+        // one execute() of a registered kernel over `nr` rows; the outputs
+        // of every column go to `outputs` (owned), column 0 is returned
+        auto run = [&](const std::string& name, const std::string& args,
+                       const StenciledElements& in, size_t nr) {
+          const KernelFactory& f =
+              kernel_registry().get(name, (DeviceType)device_type);
+          KernelConfig cfg;
+          cfg.device = dev;
+          cfg.output_device = dev;
+          if (f.output_device_type >= 0)
+            cfg.output_device = f.output_device_type == (i32)DeviceType::GPU
+                                    ? kTestDev
+                                    : CPU_DEVICE;
+          const OpInfo& info = op_registry().get(name);
+          for (auto& c : info.input_columns)
+            cfg.input_columns.push_back(c.name);
+          for (auto& c : info.output_columns)
+            cfg.output_columns.push_back(c.name);
+          cfg.args.assign(args.begin(), args.end());
+          cfg.max_batch = (i32)nr;
+          cfg.hip_stream = gpu ? per_thread_hip_stream() : nullptr;
+          std::unique_ptr<BaseKernel> kernel = f.make(cfg);
+          BatchedElements out(
+              std::max<size_t>(1, info.output_columns.size()));
+          try {
+            kernel->execute(in, out);
+          } catch (...) {
+            for (auto& col : out)
+              for (Element& e : col) outputs.elems.push_back(e);
+            if (gpu) sync_per_thread_stream();
+            throw;
+          }
+          for (auto& col : out)
+            for (Element& e : col) {
+              if (!e.is_null && e.buffer) e.device = cfg.output_device;
+              outputs.elems.push_back(e);
+            }
+          if (gpu) sync_per_thread_stream();
+          SCA_CHECK(out[0].size() == nr,
+                    "op_kernel_test: " + name + " returned " +
+                        std::to_string(out[0].size()) + " rows for " +
+                        std::to_string(nr));
+          return out[0];
+        };
+        auto download = [](const ElementVector& col) {
+          py::list res;
+          for (const Element& e : col) {
+            if (e.is_frame) {
+              SCA_CHECK(e.frame_info.size() == e.size,
+                        "op_kernel_test: frame_info disagrees with size");
+              std::vector<py::ssize_t> shape = {e.frame_info.shape[0],
+                                                e.frame_info.shape[1],
+                                                e.frame_info.shape[2]};
+              py::array a;
+              if (e.frame_info.type == FrameType::F32)
+                a = py::array_t<float>(shape);
+              else if (e.frame_info.type == FrameType::U8)
+                a = py::array_t<u8>(shape);
+              else
+                throw ScannerError("op_kernel_test: unsupported output type");
+              memcpy_buffer((u8*)a.mutable_data(), CPU_DEVICE, e.buffer,
+                            e.device, e.size);
+              res.append(a);
+            } else {
+              std::string blob(e.size, '\0');
+              memcpy_buffer((u8*)blob.data(), CPU_DEVICE, e.buffer, e.device,
+                            e.size);
+              res.append(py::bytes(blob));
+            }
+          }
+          return res;
+        };
+
+        StenciledElements in(1);
+        in[0].resize(nrows);
+        for (size_t r = 0; r < nrows; ++r)
+          for (i32 s : stencil) in[0][r].push_back(inputs.elems[r + s]);
+        ElementVector first = run(op, std::string(args_b), in, nrows);
+        if (then_op.empty()) return py::object(download(first));
+        // the first kernel's outputs stay where they are and feed a second
+        // kernel (stencil [0]), as two ops of one graph on one device do
+        StenciledElements in2(1);
+        in2[0].resize(nrows);
+        for (size_t r = 0; r < nrows; ++r) in2[0][r].push_back(first[r]);
+        ElementVector second = run(then_op, std::string(then_args_b), in2, nrows);
+        return py::object(py::make_tuple(download(first), download(second)));
+      },
+      py::arg("op_name"), py::arg("device_type"), py::arg("args_bytes"),
+      py::arg("frames"), py::arg("stencil") = std::vector<i32>{0},
+      py::arg("packed") = true, py::arg("then_op") = "",
+      py::arg("then_args") = py::bytes());
   m.def("register_python_op", &register_python_op_binding);
 
   py::class_<Database, std::shared_ptr<Database>>(m, "Database")

@@ -40,6 +40,12 @@ inline hipStream_t cur_stream() {
 // kernel sums partials per frame. Frames arrive as a device pointer array
 // (engine elements are separate allocations); outputs go to one block
 // buffer, one 3 KB slice per frame.
+// VEC: every frame of the batch starts 16-byte aligned (the host checks), so
+// the body reads dword4 vectors and chunk 0 takes the nbytes % 16 tail.
+// !VEC: some frame starts at another address (frames carved unpadded from
+// one block buffer, e.g. 13x17x3 decode output); all bytes go through the
+// byte loop and no 16-byte access is formed.
+template <bool VEC>
 __global__ void __launch_bounds__(256)
     histogram_rgb_partial_kernel(const u8* const* __restrict__ frames,
                                  u64 nbytes, u32* __restrict__ partials,
@@ -57,30 +63,37 @@ __global__ void __launch_bounds__(256)
   u32 frame = blockIdx.y;
   u32 chunk = blockIdx.x;
   const u8* in = frames[frame];
-  const uint4* in16 = reinterpret_cast<const uint4*>(in);
-  u64 nvec = nbytes / 16;
-  // grid-stride over this frame's vectors, chunk-interleaved so chunks
-  // read coalesced interleaved spans
-  for (u64 v = chunk * 256 + threadIdx.x; v < nvec;
-       v += (u64)chunks * 256) {
-    uint4 x = in16[v];
-    u64 byte0 = v * 16;
-    const u32 words[4] = {x.x, x.y, x.z, x.w};
+  if constexpr (VEC) {
+    const uint4* in16 = reinterpret_cast<const uint4*>(in);
+    u64 nvec = nbytes / 16;
+    // grid-stride over this frame's vectors, chunk-interleaved so chunks
+    // read coalesced interleaved spans
+    for (u64 v = chunk * 256 + threadIdx.x; v < nvec;
+         v += (u64)chunks * 256) {
+      uint4 x = in16[v];
+      u64 byte0 = v * 16;
+      const u32 words[4] = {x.x, x.y, x.z, x.w};
 #pragma unroll
-    for (int wi = 0; wi < 4; ++wi) {
-      u32 wv = words[wi];
+      for (int wi = 0; wi < 4; ++wi) {
+        u32 wv = words[wi];
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        u32 ch = (u32)((byte0 + wi * 4 + k) % 3);
-        atomicAdd(&lhist[rep][ch * 256 + ((wv >> (8 * k)) & 0xff)], 1u);
+        for (int k = 0; k < 4; ++k) {
+          u32 ch = (u32)((byte0 + wi * 4 + k) % 3);
+          atomicAdd(&lhist[rep][ch * 256 + ((wv >> (8 * k)) & 0xff)], 1u);
+        }
       }
     }
-  }
-  // tail bytes (nbytes % 16) handled by chunk 0
-  if (chunk == 0) {
-    u64 t0 = nvec * 16;
-    if (threadIdx.x < nbytes - t0) {
-      u64 i = t0 + threadIdx.x;
+    // tail bytes (nbytes % 16) handled by chunk 0
+    if (chunk == 0) {
+      u64 t0 = nvec * 16;
+      if (threadIdx.x < nbytes - t0) {
+        u64 i = t0 + threadIdx.x;
+        atomicAdd(&lhist[rep][(u32)(i % 3) * 256 + in[i]], 1u);
+      }
+    }
+  } else {
+    for (u64 i = (u64)chunk * 256 + threadIdx.x; i < nbytes;
+         i += (u64)chunks * 256) {
       atomicAdd(&lhist[rep][(u32)(i % 3) * 256 + in[i]], 1u);
     }
   }
@@ -179,8 +192,17 @@ class HistogramKernelGPU : public BatchedKernel {
     u8* out_block =
         new_block_buffer(config_.device, (u64)n * 768 * 4, (i32)n);
     dim3 grid(chunks, (u32)n);
-    histogram_rgb_partial_kernel<<<grid, 256, 0, s>>>(
-        (const u8* const*)d_ptrs, nbytes, (u32*)scratch, chunks);
+    // dword4 loads only when every frame of the batch starts on a 16-byte
+    // boundary; otherwise the byte-wise instantiation
+    uintptr_t addr_bits = 0;
+    for (const u8* p : ptrs) addr_bits |= (uintptr_t)p;
+    if ((addr_bits & 15) == 0) {
+      histogram_rgb_partial_kernel<true><<<grid, 256, 0, s>>>(
+          (const u8* const*)d_ptrs, nbytes, (u32*)scratch, chunks);
+    } else {
+      histogram_rgb_partial_kernel<false><<<grid, 256, 0, s>>>(
+          (const u8* const*)d_ptrs, nbytes, (u32*)scratch, chunks);
+    }
     HIPK_CHECK(hipGetLastError());
     // reduce fills the chip by splitting the chunk dimension; >1 slice
     // needs a zeroed output for the atomic merge

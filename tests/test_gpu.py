@@ -156,7 +156,10 @@ def test_gpu_color_ops_match_cpu(sc):
         gpu = run(sp.DeviceType.GPU, f"g_c_{name}_gpu", mk)
         assert cpu.shape == gpu.shape, name
         diff = np.abs(cpu.astype(int) - gpu.astype(int))
-        assert diff.max() <= 1, (name, diff.max())
+        # crop, planar and blur are integer operations: equal; gray and yuv
+        # round a float (held to the float64 value in test_image_ops_gpu.py)
+        bound = 1 if name in ("gray", "yuv") else 0
+        assert diff.max() <= bound, (name, diff.max())
 
 
 def test_gpu_to_cpu_device_crossing(sc):

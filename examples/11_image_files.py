@@ -53,7 +53,9 @@ print(f"{os.path.basename(paths[0])}: {info['h']}x{info['w']}x{info['c']}, "
 
 # ---- job 2: the stills come back in, are halved and written out again ----
 img = sc.sources.Files(paths)
-frame = sc.ops.ImageDecoder(img=img, device=dev)
+# serial_scan="device" also decodes JPEG files *without* restart markers on
+# the GPU (camera, browser and default Pillow files); the default is "host"
+frame = sc.ops.ImageDecoder(img=img, serial_scan="device", device=dev)
 thumb = sc.ops.Resize(frame=frame, width=64, height=48, device=dev)
 out = sc.ops.ImageEncoder(frame=thumb, format="jpg", quality=85, device=dev)
 thumbs = os.path.join(tmp, "thumbs")

@@ -22,6 +22,7 @@
 #include "video/mp4.h"
 #include "ops/image_decode.h"
 #include "ops/jpeg_common.h"
+#include "ops/jpeg_sync_common.h"
 #include "ops/kernel.h"
 #include "ops/python_kernel.h"
 #include "video/svc.h"
@@ -1064,13 +1065,48 @@ PYBIND11_MODULE(_core, m) {
           }
           return out;
         });
+  // The self-synchronising decoder's CPU model (ops/jpeg_sync_cpu.cpp) on a
+  // JPEG without restart markers -> ([H,W,C] u8, stats dict). chunk_bytes 0
+  // is the default, jpeg_sync_chunk_bytes().
+  m.def("jpeg_sync_chunk_bytes", []() { return kJpegSyncChunkBytes; });
+  m.def("jpeg_sync_model",
+        [](py::bytes blob, u32 chunk_bytes) {
+          std::string s = blob;
+          JpegInfo in = jpeg_parse((const u8*)s.data(), s.size());
+          py::array_t<u8> a({(i64)in.g.h, (i64)in.g.w, (i64)in.g.nc});
+          JpegSyncStats st;
+          jpeg_decode_sync_model((const u8*)s.data(), in, chunk_bytes,
+                                 a.mutable_data(), &st);
+          py::dict d;
+          d["chunks"] = st.chunks;
+          d["groups"] = st.groups;
+          d["group_iterations"] = st.group_iterations;
+          d["cross_rounds"] = st.cross_rounds;
+          d["cross_repairs"] = st.cross_repairs;
+          d["stuffed_starts"] = st.stuffed_starts;
+          d["empty_chunks"] = st.empty_chunks;
+          d["status"] = st.status;
+          d["verified"] = st.verified;
+          d["fallback"] = !st.verified;
+          return py::make_tuple(a, d);
+        },
+        py::arg("blob"), py::arg("chunk_bytes") = 0);
   // One batch through jpeg_decode_gpu -> list of [H,W,C] u8 arrays, in
   // order; with host_rows=True also the number of rows the CPU decoders
-  // handled (JPEG without DRI, PNG).
+  // handled (PNG; JPEG without DRI unless serial_scan="device", and then
+  // those that failed verification); with stats=True also a dict of the
+  // self-synchronising decoder's row counts.
   m.def("jpeg_gpu_decode",
-        [](const std::vector<py::bytes>& blobs, bool want_host_rows)
+        [](const std::vector<py::bytes>& blobs, bool want_host_rows,
+           const std::string& serial_scan, u32 chunk_bytes, bool want_stats)
             -> py::object {
           SCA_CHECK(have_gpu(), "jpeg_gpu_decode needs a GPU");
+          SCA_CHECK(serial_scan == "host" || serial_scan == "device",
+                    "serial_scan must be 'host' or 'device', got '" +
+                        serial_scan + "'");
+          JpegGpuOptions opt;
+          opt.serial_scan_on_device = serial_scan == "device";
+          opt.chunk_bytes = chunk_bytes;
           DeviceHandle dev{DeviceType::GPU, 0};
           std::vector<std::string> data(blobs.begin(), blobs.end());
           std::vector<ImageBlob> ib;
@@ -1088,8 +1124,9 @@ PYBIND11_MODULE(_core, m) {
           }
           std::vector<DeviceFrame> frames;
           i64 host_rows = 0;
+          JpegGpuStats gs;
           jpeg_decode_gpu(ib, infos, dev, per_thread_hip_stream(), frames,
-                          &host_rows);
+                          &host_rows, opt, &gs);
           py::list res;
           try {
             for (auto& f : frames) {
@@ -1103,19 +1140,35 @@ PYBIND11_MODULE(_core, m) {
             throw;
           }
           for (auto& f : frames) delete_buffer(dev, f.buffer);
+          py::dict sd;
+          sd["sync_rows"] = gs.sync_rows;
+          sd["fallback_rows"] = gs.fallback_rows;
+          if (want_host_rows && want_stats)
+            return py::make_tuple(res, host_rows, sd);
           if (want_host_rows) return py::make_tuple(res, host_rows);
+          if (want_stats) return py::make_tuple(res, sd);
           return std::move(res);
         },
-        py::arg("blobs"), py::arg("host_rows") = false);
+        py::arg("blobs"), py::arg("host_rows") = false,
+        py::arg("serial_scan") = "host", py::arg("chunk_bytes") = 0,
+        py::arg("stats") = false);
   // Seconds of each of `iters` decodes of the batch, every one ending with
   // the frames resident in HBM. mode "gpu": jpeg_parse + jpeg_decode_gpu
-  // (compressed H2D inside). mode "cpu": jpeg_decode_cpu on this thread,
+  // (compressed H2D inside; serial_scan and chunk_bytes as for
+  // jpeg_gpu_decode). mode "cpu": jpeg_decode_cpu on this thread,
   // then H2D of the raw frames. mode "upload": the blobs are raw pixels
   // already (another decoder's output); one host copy and the H2D.
   m.def("jpeg_decode_bench",
         [](const std::vector<py::bytes>& blobs, i32 iters,
-           const std::string& mode) {
+           const std::string& mode, const std::string& serial_scan,
+           u32 chunk_bytes) {
           SCA_CHECK(have_gpu(), "jpeg_decode_bench needs a GPU");
+          SCA_CHECK(serial_scan == "host" || serial_scan == "device",
+                    "serial_scan must be 'host' or 'device', got '" +
+                        serial_scan + "'");
+          JpegGpuOptions opt;
+          opt.serial_scan_on_device = serial_scan == "device";
+          opt.chunk_bytes = chunk_bytes;
           SCA_CHECK(mode == "gpu" || mode == "cpu" || mode == "upload",
                     "mode must be 'gpu', 'cpu' or 'upload'");
           SCA_CHECK(!blobs.empty() && iters > 0, "empty benchmark");
@@ -1134,7 +1187,7 @@ PYBIND11_MODULE(_core, m) {
               }
               std::vector<DeviceFrame> frames;
               jpeg_decode_gpu(ib, infos, dev, per_thread_hip_stream(),
-                              frames);
+                              frames, nullptr, opt);
               secs.push_back(std::chrono::duration<double>(
                                  std::chrono::steady_clock::now() - t0)
                                  .count());
@@ -1172,7 +1225,8 @@ PYBIND11_MODULE(_core, m) {
           }
           return secs;
         },
-        py::arg("blobs"), py::arg("iters") = 1, py::arg("mode") = "gpu");
+        py::arg("blobs"), py::arg("iters") = 1, py::arg("mode") = "gpu",
+        py::arg("serial_scan") = "host", py::arg("chunk_bytes") = 0);
   // seconds the calling thread's last jpeg_decode_gpu waited in its stream
   // synchronise (the rest of the call is host work: parse, pack, enqueue)
   m.def("jpeg_decode_last_sync_seconds", &jpeg_decode_gpu_last_sync_seconds);

@@ -1,7 +1,8 @@
 // Still-image decode: baseline JPEG and 8-bit PNG files -> HWC u8 frames.
 // The CPU decoders (jpeg_decode_cpu.cpp, png_decode.cpp) are HIP-free and
-// define the pixels; kernels/jpeg_decode.hip reproduces the JPEG ones on the
-// GPU from the same arithmetic (jpeg_decode_common.h).
+// define the pixels; kernels/jpeg_decode.hip and
+// kernels/jpeg_sync_decode.hip reproduce the JPEG ones on the GPU from the
+// same arithmetic (jpeg_decode_common.h, jpeg_sync_common.h).
 //
 // Accepted JPEG: SOF0, or SOF1 at 8-bit precision; 1 component, or 3
 // components taken as YCbCr with luma sampling 1x1, 2x1 or 2x2 and chroma
@@ -48,6 +49,26 @@ void jpeg_decode_cpu_into(const u8* data, const JpegInfo& info, u8* out);
 // Text of an entropy error, shared with the GPU decoder's report.
 std::string jpeg_entropy_error(u32 status, u32 segment);
 
+// ---- model of the self-synchronising decoder (jpeg_sync_cpu.cpp) ----
+struct JpegSyncStats {
+  u32 chunks = 0, groups = 0;
+  u32 group_iterations = 0;  // most iterations any in-group loop ran
+  u32 cross_rounds = 0;      // last round across groups that changed an exit
+  u32 cross_repairs = 0;     // groups repaired in those rounds
+  u32 stuffed_starts = 0;    // chunks that started on a stuffed 00
+  u32 empty_chunks = 0;      // chunks that hold no symbol boundary
+  u32 status = 0;            // 0, or JpegBlockStatus / JpegSyncStatus
+  bool verified = false;     // else the pixels are jpeg_decode_cpu_into's
+};
+// The kernels' algorithm on one file without restart markers, lane by lane:
+// the same pixels into h*w*c bytes at `out` and the same verdict. A file
+// that fails verification is decoded by jpeg_decode_cpu_into (which raises
+// on a corrupt one) after *stats has been written. chunk_bytes 0 is the
+// default.
+void jpeg_decode_sync_model(const u8* data, const JpegInfo& info,
+                            u32 chunk_bytes, u8* out,
+                            JpegSyncStats* stats = nullptr);
+
 // IHDR only: the output shape (c is 1 or 3), after the same checks
 // png_decode makes on the header.
 void png_shape(const u8* data, size_t size, i32& h, i32& w, i32& c);
@@ -70,16 +91,35 @@ struct DeviceFrame {
 // Decodes a batch of files (any mix of shapes, samplings and tables) into
 // device frames, in order. infos[i] is jpeg_parse of blobs[i] for a JPEG row
 // and is ignored for a PNG row. JPEG rows with a DRI segment are decoded on
-// the device, one lane per restart segment; JPEG rows without one and PNG
-// rows are decoded by the CPU decoders and uploaded (*host_rows counts
-// them). Everything is issued on `stream`, which is synchronised once, after
-// the per-file status words have been copied back; a corrupt row raises
-// ScannerError naming the row and no frame of the call survives. The frames
-// share one block buffer: release each with delete_buffer(dev, buffer).
+// the device, one lane per restart segment. JPEG rows without one are
+// decoded by the CPU decoder and uploaded, unless
+// opt.serial_scan_on_device asks for the self-synchronising decoder
+// (kernels/jpeg_sync_decode.hip, jpeg_sync_common.h): one lane per chunk of
+// opt.chunk_bytes, verified on the device; a row that fails the
+// verification is decoded by jpeg_decode_cpu_into after the synchronise and
+// uploaded, so its pixels or its error are always the CPU decoder's. PNG
+// rows are decoded by the CPU decoder. *host_rows counts every row the CPU
+// decoders handled. Everything is issued on `stream`, which is synchronised
+// once, after the per-file status words have been copied back (once more
+// when a row fell back); a corrupt row raises ScannerError naming the row
+// and no frame of the call survives. The frames share one block buffer:
+// release each with delete_buffer(dev, buffer).
+struct JpegGpuOptions {
+  bool serial_scan_on_device = false;
+  u32 chunk_bytes = 0;  // 0: kJpegSyncChunkBytes; else a power of two >= 4
+};
+struct JpegGpuStats {
+  i64 sync_rows = 0;      // rows the self-synchronising decoder delivered
+  i64 fallback_rows = 0;  // rows it gave back to the CPU decoder
+};
 void jpeg_decode_gpu(const std::vector<ImageBlob>& blobs,
                      const std::vector<JpegInfo>& infos, DeviceHandle dev,
                      void* stream, std::vector<DeviceFrame>& out_frames,
-                     i64* host_rows = nullptr);
+                     i64* host_rows = nullptr, JpegGpuOptions opt = {},
+                     JpegGpuStats* stats = nullptr);
+// The ImageDecoder argument serial_scan ("host", the default, or "device")
+// from an op instance's msgpack args; any other value is rejected by name.
+bool image_decoder_serial_scan_on_device(const std::vector<u8>& args);
 // Seconds the calling thread's last jpeg_decode_gpu spent waiting in its
 // stream synchronise.
 double jpeg_decode_gpu_last_sync_seconds();

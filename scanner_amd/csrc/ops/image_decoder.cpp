@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "../memory.h"
+#include "../msgpack.h"
 #include "image_decode.h"
 #include "kernel.h"
 
@@ -15,7 +16,12 @@ namespace {
 
 class ImageDecoderKernelCPU : public BatchedKernel {
  public:
-  using BatchedKernel::BatchedKernel;
+  explicit ImageDecoderKernelCPU(const KernelConfig& cfg)
+      : BatchedKernel(cfg) {
+    // where a GPU kernel decodes scans without restart markers; nothing to
+    // choose here, but a graph may carry the argument on either device
+    image_decoder_serial_scan_on_device(cfg.args);
+  }
   void execute_batch(const BatchedElements& in, BatchedElements& out) override {
     for (size_t i = 0; i < in[0].size(); ++i) {
       const Element& b = in[0][i];
@@ -48,6 +54,13 @@ class ImageDecoderKernelCPU : public BatchedKernel {
 };
 
 }  // namespace
+
+bool image_decoder_serial_scan_on_device(const std::vector<u8>& args) {
+  std::string v = mp::decode(args).get_str("serial_scan", "host");
+  SCA_CHECK(v == "host" || v == "device",
+            "ImageDecoder supports serial_scan=host|device, got '" + v + "'");
+  return v == "device";
+}
 
 void register_image_decoder_op() {
   static bool done = false;

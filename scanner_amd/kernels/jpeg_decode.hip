@@ -5,8 +5,12 @@
 //
 // A JPEG scan is one serial bit stream except at restart markers, where the
 // DC prediction and the bit alignment start afresh; so the unit of
-// parallelism is the restart segment. Files without a DRI segment (and PNG
-// files) are decoded by the CPU decoders and uploaded.
+// parallelism is the restart segment. PNG files are decoded by the CPU
+// decoder and uploaded; so are files without a DRI segment, unless the
+// caller asks for the self-synchronising decoder of
+// kernels/jpeg_sync_decode.hip, which this file's host side feeds from the
+// same staging buffer and whose rows share the colour kernel and the status
+// words (records of both: kernels/jpeg_decode_dev.h).
 //
 // Per batch (any mix of shapes, samplings and tables):
 //   host     parse every file; pack status words, one descriptor per file
@@ -40,6 +44,7 @@
 #include "../csrc/memory.h"
 #include "../csrc/ops/image_decode.h"
 #include "../csrc/ops/kernel.h"
+#include "jpeg_decode_dev.h"
 
 namespace sca {
 
@@ -59,40 +64,7 @@ constexpr u32 kSlotStride = 66;   // int16 per lane slot: 33 words, so lanes
                                   // reading the same coefficient hit
                                   // different banks
 constexpr u32 kColourThreads = 256;
-constexpr u32 kNoError = 0xffffffffu;
-
-struct JpegDecFile {
-  JpegDecGeom g;
-  u32 status_index;
-  u32 pad;
-  u64 plane_off[3];  // into the plane workspace; unused for grey
-  u8* out;           // HWC u8
-  u16 q[3][64];
-  u8 zz2nat[64];
-  JpegHuff dc[3], ac[3];
-};
-static_assert(sizeof(JpegDecFile) % 8 == 0, "descriptors are copied as words");
-
-struct JpegDecGroup {
-  u32 file;
-  u32 seg0;        // first segment record of the workgroup
-  u32 nseg;        // lanes in use
-  u32 file_seg0;   // index of that segment inside its file
-};
-struct JpegDecSeg {
-  u32 begin, end;  // into the packed entropy bytes
-  u32 first_mcu, mcu_count;
-};
-
-struct JpegDecArgs {
-  const JpegDecFile* files;
-  const JpegDecGroup* groups;
-  const JpegDecSeg* segs;
-  const u8* entropy;
-  u8* planes;
-  u32* status;
-  u32 nfiles;
-};
+constexpr u32 kNoError = kJpegDecNoError;
 
 __global__ void __launch_bounds__(kLanes) jpeg_entropy_idct_kernel(
     JpegDecArgs a) {
@@ -140,29 +112,11 @@ __global__ void __launch_bounds__(kLanes) jpeg_entropy_idct_kernel(
       u8 pix[64];
       jpeg_idct_block(deq, pix);
       if (g.nc == 1) {
-        // the image itself: only the part of the block inside it
-        u8* dst = f.out;
-#pragma unroll
-        for (u32 y = 0; y < 8; ++y) {
-          if (py + y >= (u32)g.h) break;
-#pragma unroll
-          for (u32 x = 0; x < 8; ++x) {
-            if (px + x < (u32)g.w)
-              dst[(u64)(py + y) * (u32)g.w + px + x] = pix[y * 8 + x];
-          }
-        }
+        jpeg_store_block_grey(pix, f.out, (u32)g.h, (u32)g.w, px, py);
       } else {
         u32 stride = comp == 0 ? g.y_stride : g.c_stride;
-        u8* dst = a.planes + f.plane_off[comp] + (u64)py * stride + px;
-#pragma unroll
-        for (u32 y = 0; y < 8; ++y) {
-          uint2 v;
-          v.x = pix[y * 8] | pix[y * 8 + 1] << 8 | pix[y * 8 + 2] << 16 |
-                (u32)pix[y * 8 + 3] << 24;
-          v.y = pix[y * 8 + 4] | pix[y * 8 + 5] << 8 | pix[y * 8 + 6] << 16 |
-                (u32)pix[y * 8 + 7] << 24;
-          *reinterpret_cast<uint2*>(dst + (u64)y * stride) = v;
-        }
+        jpeg_store_block_plane(
+            pix, a.planes + f.plane_off[comp] + (u64)py * stride + px, stride);
       }
     }
   }
@@ -219,29 +173,43 @@ double jpeg_decode_gpu_last_sync_seconds() { return t_last_sync; }
 void jpeg_decode_gpu(const std::vector<ImageBlob>& blobs,
                      const std::vector<JpegInfo>& infos, DeviceHandle dev,
                      void* stream, std::vector<DeviceFrame>& out_frames,
-                     i64* host_rows) {
+                     i64* host_rows, JpegGpuOptions opt,
+                     JpegGpuStats* stats) {
   SCA_CHECK(dev.is_gpu(), "jpeg_decode_gpu needs a GPU device");
   SCA_CHECK(infos.size() == blobs.size(), "one JpegInfo per blob");
   size_t n = blobs.size();
   out_frames.assign(n, DeviceFrame{});
   if (host_rows) *host_rows = 0;
+  if (stats) *stats = JpegGpuStats{};
+  u32 chunk_bytes = opt.chunk_bytes ? opt.chunk_bytes : kJpegSyncChunkBytes;
+  SCA_CHECK(jpeg_sync_valid_chunk_bytes(chunk_bytes),
+            "chunk_bytes must be a power of two >= 4, got " +
+                std::to_string(chunk_bytes));
   if (n == 0) return;
   JPEG_DEC_CHECK(hipSetDevice(dev.id));
   hipStream_t s = (hipStream_t)stream;
 
   // ---- classify, decode the host rows, lay out the outputs ----
-  std::vector<int> kind(n, 0);  // 0 null, 1 device, 2 host
+  // 0 null, 1 device by restart segments, 2 host, 3 device by chunks
+  std::vector<int> kind(n, 0);
+  auto on_device = [&](size_t i) { return kind[i] == 1 || kind[i] == 3; };
   std::vector<DecodedImage> host_img(n);
   std::vector<u64> out_off(n, 0);
   u64 out_total = 0, host_pix_total = 0;
   i32 live = 0;
-  size_t ndev = 0;
+  size_t ndev = 0, nsync = 0;
   for (size_t i = 0; i < n; ++i) {
     if (!blobs[i].data) continue;
     DeviceFrame& fr = out_frames[i];
-    if (is_jpeg(blobs[i].data, blobs[i].size) &&
-        infos[i].restart_interval != 0) {
-      kind[i] = 1;
+    bool jpeg = is_jpeg(blobs[i].data, blobs[i].size);
+    bool by_chunks =
+        jpeg && opt.serial_scan_on_device && infos[i].restart_interval == 0 &&
+        infos[i].segments.size() == 1 &&
+        infos[i].segments[0].end - infos[i].segments[0].begin <
+            kJpegSyncMaxScanBytes;
+    if ((jpeg && infos[i].restart_interval != 0) || by_chunks) {
+      kind[i] = by_chunks ? 3 : 1;
+      nsync += by_chunks;
       ++ndev;
       fr.h = infos[i].g.h;
       fr.w = infos[i].g.w;
@@ -276,15 +244,23 @@ void jpeg_decode_gpu(const std::vector<ImageBlob>& blobs,
   }
   if (live == 0) return;
 
-  // ---- staging layout: status | files | groups | segments | entropy |
-  // (host only) pixels of the host rows ----
-  size_t ngroups = 0, nsegs = 0;
-  u64 entropy_total = 0, planes_total = 0;
+  // ---- staging layout: status | files | groups | segments | chunked
+  // files | their groups | entropy | (host only) pixels of the host rows ----
+  size_t ngroups = 0, nsegs = 0, nsgroups = 0, nchunks = 0;
+  u64 entropy_total = 0, planes_total = 0, coef_total = 0;
   for (size_t i = 0; i < n; ++i) {
-    if (kind[i] != 1) continue;
+    if (!on_device(i)) continue;
     const JpegInfo& in = infos[i];
-    nsegs += in.segments.size();
-    ngroups += (in.segments.size() + kLanes - 1) / kLanes;
+    if (kind[i] == 3) {
+      u32 nc = jpeg_sync_chunk_count(
+          in.segments[0].end - in.segments[0].begin, chunk_bytes);
+      nchunks += nc;
+      nsgroups += (nc + kJpegSyncGroupChunks - 1) / kJpegSyncGroupChunks;
+      coef_total += (u64)in.g.nmcu * in.g.blocks_per_mcu * 64;
+    } else {
+      nsegs += in.segments.size();
+      ngroups += (in.segments.size() + kLanes - 1) / kLanes;
+    }
     entropy_total +=
         align_up(in.segments.back().end - in.segments.front().begin, 16);
     if (in.g.nc == 3)
@@ -295,8 +271,19 @@ void jpeg_decode_gpu(const std::vector<ImageBlob>& blobs,
   u64 files_off = align_up(status_off + 4 * ndev, 256);
   u64 groups_off = align_up(files_off + sizeof(JpegDecFile) * ndev, 256);
   u64 segs_off = align_up(groups_off + sizeof(JpegDecGroup) * ngroups, 256);
-  u64 entropy_off = align_up(segs_off + sizeof(JpegDecSeg) * nsegs, 256);
+  u64 sfiles_off = align_up(segs_off + sizeof(JpegDecSeg) * nsegs, 256);
+  u64 sgroups_off = align_up(sfiles_off + sizeof(JpegSyncFile) * nsync, 256);
+  u64 entropy_off =
+      align_up(sgroups_off + sizeof(JpegSyncGroup) * nsgroups, 256);
   u64 upload = align_up(entropy_off + entropy_total, 256);
+  // device only, behind the upload: planes | chunk records | first blocks |
+  // group exits | coefficients
+  u64 chunks_off = align_up(upload + planes_total, 256);
+  u64 first_off = align_up(chunks_off + sizeof(JpegSyncChunk) * nchunks, 256);
+  u64 gexit_off = align_up(first_off + 4 * nchunks, 256);
+  u64 coef_off =
+      align_up(gexit_off + 2 * sizeof(JpegSyncState) * nsgroups, 256);
+  u64 ws_size = coef_off + coef_total * sizeof(i16);
   u64 host_pix_off = upload;
   u64 status_back_off = host_pix_off + host_pix_total;
   u64 staging_size = status_back_off + align_up(4 * ndev, 256) + 256;
@@ -304,11 +291,13 @@ void jpeg_decode_gpu(const std::vector<ImageBlob>& blobs,
 
   u8* out_block = nullptr;
   u8* staging = nullptr;
-  u8* ws = nullptr;  // device: the uploaded part, then the planes
+  u8* fallback = nullptr;  // pinned: pixels of the rows that fell back
+  u8* ws = nullptr;  // device: the uploaded part, then the workspaces
   auto release = [&](bool outputs_too) {
     if (staging) delete_buffer(CPU_DEVICE, staging);
+    if (fallback) delete_buffer(CPU_DEVICE, fallback);
     if (ws) delete_buffer(dev, ws);
-    staging = ws = nullptr;
+    staging = fallback = ws = nullptr;
     if (outputs_too && out_block) {
       for (i32 k = 0; k < live; ++k) delete_buffer(dev, out_block);
       out_block = nullptr;
@@ -318,7 +307,7 @@ void jpeg_decode_gpu(const std::vector<ImageBlob>& blobs,
   try {
     out_block = new_block_buffer(dev, out_total, live);
     staging = new_buffer(CPU_DEVICE, staging_size);
-    if (ndev) ws = new_buffer(dev, upload + planes_total);
+    if (ndev) ws = new_buffer(dev, ws_size);
     for (size_t i = 0; i < n; ++i)
       if (kind[i]) out_frames[i].buffer = out_block + out_off[i];
 
@@ -329,10 +318,13 @@ void jpeg_decode_gpu(const std::vector<ImageBlob>& blobs,
       auto* groups = reinterpret_cast<JpegDecGroup*>(staging + groups_off);
       auto* segs = reinterpret_cast<JpegDecSeg*>(staging + segs_off);
       u8* entropy = staging + entropy_off;
-      u32 fi = 0, gi = 0, si = 0;
-      u64 epos = 0, ppos = 0;
+      auto* sfiles = reinterpret_cast<JpegSyncFile*>(staging + sfiles_off);
+      auto* sgroups = reinterpret_cast<JpegSyncGroup*>(staging + sgroups_off);
+      u32 fi = 0, gi = 0, si = 0, sfi = 0, sgi = 0, ci = 0;
+      u32 max_rounds = 0, max_nblk = 0;
+      u64 epos = 0, ppos = 0, cpos = 0;
       for (size_t i = 0; i < n; ++i) {
-        if (kind[i] != 1) continue;
+        if (!on_device(i)) continue;
         const JpegInfo& in = infos[i];
         status[fi] = kNoError;
         JpegDecFile& f = files[fi];
@@ -361,13 +353,35 @@ void jpeg_decode_gpu(const std::vector<ImageBlob>& blobs,
         u32 base = in.segments.front().begin;
         u32 len = in.segments.back().end - base;
         std::memcpy(entropy + epos, blobs[i].data + base, len);
-        u32 nseg = (u32)in.segments.size();
-        for (u32 k = 0; k < nseg; k += kLanes)
-          groups[gi++] = {fi, si + k, std::min(kLanes, nseg - k), k};
-        for (const JpegSegment& sg : in.segments)
-          segs[si++] = {(u32)(epos + sg.begin - base),
-                        (u32)(epos + sg.end - base), sg.first_mcu,
-                        sg.mcu_count};
+        if (kind[i] == 3) {
+          JpegSyncFile& sf = sfiles[sfi];
+          std::memset(&sf, 0, sizeof(sf));
+          sf.file = fi;
+          sf.begin = (u32)epos;
+          sf.end = (u32)(epos + len);
+          sf.chunk_bytes = chunk_bytes;
+          sf.nchunks = jpeg_sync_chunk_count(len, chunk_bytes);
+          sf.chunk0 = ci;
+          sf.ngroups =
+              (sf.nchunks + kJpegSyncGroupChunks - 1) / kJpegSyncGroupChunks;
+          sf.rounds = jpeg_sync_rounds(sf.ngroups);
+          sf.nblk = in.g.nmcu * in.g.blocks_per_mcu;
+          sf.coef_off = cpos;
+          for (u32 k = 0; k < sf.ngroups; ++k) sgroups[sgi++] = {sfi, k};
+          ci += sf.nchunks;
+          cpos += (u64)sf.nblk * 64;
+          max_rounds = std::max(max_rounds, sf.rounds);
+          max_nblk = std::max(max_nblk, sf.nblk);
+          ++sfi;
+        } else {
+          u32 nseg = (u32)in.segments.size();
+          for (u32 k = 0; k < nseg; k += kLanes)
+            groups[gi++] = {fi, si + k, std::min(kLanes, nseg - k), k};
+          for (const JpegSegment& sg : in.segments)
+            segs[si++] = {(u32)(epos + sg.begin - base),
+                          (u32)(epos + sg.end - base), sg.first_mcu,
+                          sg.mcu_count};
+        }
         epos += align_up(len, 16);
         ++fi;
       }
@@ -381,8 +395,26 @@ void jpeg_decode_gpu(const std::vector<ImageBlob>& blobs,
       a.entropy = ws + entropy_off;
       a.planes = ws + upload;
       a.nfiles = (u32)ndev;
-      jpeg_entropy_idct_kernel<<<(u32)ngroups, kLanes, 0, s>>>(a);
-      JPEG_DEC_CHECK(hipGetLastError());
+      if (ngroups) {
+        jpeg_entropy_idct_kernel<<<(u32)ngroups, kLanes, 0, s>>>(a);
+        JPEG_DEC_CHECK(hipGetLastError());
+      }
+      if (nsync) {
+        JpegSyncArgs sa{};
+        sa.dec = a;
+        sa.sfiles = reinterpret_cast<const JpegSyncFile*>(ws + sfiles_off);
+        sa.sgroups = reinterpret_cast<const JpegSyncGroup*>(ws + sgroups_off);
+        sa.chunks = reinterpret_cast<JpegSyncChunk*>(ws + chunks_off);
+        sa.first_block = reinterpret_cast<u32*>(ws + first_off);
+        sa.gexit = reinterpret_cast<JpegSyncState*>(ws + gexit_off);
+        sa.coef = reinterpret_cast<i16*>(ws + coef_off);
+        sa.coef_count = coef_total;
+        sa.nsfiles = (u32)nsync;
+        sa.nsgroups = (u32)nsgroups;
+        sa.max_rounds = max_rounds;
+        sa.max_nblk = max_nblk;
+        jpeg_sync_enqueue(sa, s);
+      }
       if (max_colour_blocks) {
         jpeg_colour_kernel<<<dim3(max_colour_blocks, (u32)ndev),
                              kColourThreads, 0, s>>>(a);
@@ -411,13 +443,45 @@ void jpeg_decode_gpu(const std::vector<ImageBlob>& blobs,
       const u32* back =
           reinterpret_cast<const u32*>(staging + status_back_off);
       u32 fi = 0;
+      std::vector<size_t> fell_back;
+      u64 fallback_total = 0;
       for (size_t i = 0; i < n; ++i) {
-        if (kind[i] != 1) continue;
+        if (!on_device(i)) continue;
         u32 st = back[fi++];
-        if (st != kNoError)
+        if (st == kNoError) continue;
+        if (kind[i] == 1)
           throw ScannerError("ImageDecoder: row " + std::to_string(i) +
                              " of the batch: check failed: " +
                              jpeg_entropy_error(st & 15u, st >> 4));
+        // a chunked row that failed verification: the CPU decoder's pixels,
+        // or its error
+        DecodedImage& img = host_img[i];
+        img.pixels.resize((size_t)infos[i].g.h * infos[i].g.w * infos[i].g.nc);
+        try {
+          jpeg_decode_cpu_into(blobs[i].data, infos[i], img.pixels.data());
+        } catch (const ScannerError& err) {
+          throw ScannerError("ImageDecoder: row " + std::to_string(i) +
+                             " of the batch: " + err.what());
+        }
+        fell_back.push_back(i);
+        fallback_total += align_up(img.pixels.size(), 256);
+      }
+      if (!fell_back.empty()) {
+        fallback = new_buffer(CPU_DEVICE, fallback_total);
+        u64 fpos = 0;
+        for (size_t i : fell_back) {
+          size_t sz = host_img[i].pixels.size();
+          std::memcpy(fallback + fpos, host_img[i].pixels.data(), sz);
+          JPEG_DEC_CHECK(hipMemcpyAsync(out_frames[i].buffer, fallback + fpos,
+                                        sz, hipMemcpyHostToDevice, s));
+          fpos += align_up(sz, 256);
+        }
+        JPEG_DEC_CHECK(hipStreamSynchronize(s));
+        if (host_rows) *host_rows += (i64)fell_back.size();
+      }
+      if (stats) {
+        stats->fallback_rows = (i64)fell_back.size();
+        stats->sync_rows = (i64)nsync - stats->fallback_rows;
       }
     }
   } catch (...) {
@@ -435,7 +499,10 @@ namespace {
 // the entropy-coded bytes of the whole batch at once.
 class ImageDecoderKernelGPU : public BatchedKernel {
  public:
-  using BatchedKernel::BatchedKernel;
+  explicit ImageDecoderKernelGPU(const KernelConfig& cfg)
+      : BatchedKernel(cfg) {
+    opt_.serial_scan_on_device = image_decoder_serial_scan_on_device(cfg.args);
+  }
 
   void execute_batch(const BatchedElements& in, BatchedElements& out) override {
     const ElementVector& col = in[0];
@@ -446,6 +513,7 @@ class ImageDecoderKernelGPU : public BatchedKernel {
     std::vector<u8*> host_copies;
     std::vector<DeviceFrame> frames;
     i64 host_rows = 0, live = 0;
+    JpegGpuStats stats;
     try {
       for (size_t i = 0; i < n; ++i) {
         const Element& b = col[i];
@@ -474,7 +542,7 @@ class ImageDecoderKernelGPU : public BatchedKernel {
       void* stream =
           config_.hip_stream ? config_.hip_stream : per_thread_hip_stream();
       jpeg_decode_gpu(blobs, infos, config_.device, stream, frames,
-                      &host_rows);
+                      &host_rows, opt_, &stats);
     } catch (...) {
       for (u8* h : host_copies) delete_buffer(CPU_DEVICE, h);
       throw;
@@ -498,8 +566,16 @@ class ImageDecoderKernelGPU : public BatchedKernel {
     if (config_.profiler) {
       config_.profiler->increment("jpeg_gpu_decode_frames", live - host_rows);
       config_.profiler->increment("image_decode_host_rows", host_rows);
+      if (opt_.serial_scan_on_device) {
+        config_.profiler->increment("jpeg_gpu_sync_frames", stats.sync_rows);
+        config_.profiler->increment("jpeg_sync_fallback_rows",
+                                    stats.fallback_rows);
+      }
     }
   }
+
+ private:
+  JpegGpuOptions opt_;
 };
 
 }  // namespace

@@ -4,14 +4,24 @@
 _core.jpeg_decode_bench on batches of 8 1080p files in host memory, each
 timed call ending with the decoded frames resident in HBM:
 
-  gpu     jpeg_parse + jpeg_decode_gpu (compressed H2D inside)
+  gpu     jpeg_parse + jpeg_decode_gpu (compressed H2D inside); files
+          without restart markers are decoded on the host inside the call
+          (serial_scan="host", the default)
+  gpu_sync, gpu_sync_<bytes>
+          the same call with serial_scan="device": the self-synchronising
+          decoder at the default chunk size, and at 32, 64, 128 and 256
+          bytes (only for the files without restart markers)
   cpu     jpeg_decode_cpu on one core + H2D of the raw frames (the same
           pixels as the gpu side)
   pillow  Pillow decode + H2D of the raw frames (informational: a different
           decoder)
 
-Files: our encoder at quality 90 ("smooth" and "noise", restart interval 32)
-and Pillow 4:2:0 with a restart marker per MCU row. The sides alternate in
+Files: our encoder at quality 90 ("smooth" and "noise", restart interval 32),
+Pillow 4:2:0 with a restart marker per MCU row, and "pillow420_plain": Pillow
+4:2:0 without restart markers, smooth and noise. For the latter the CPU
+model's chunk, group and round counts of the first file and the rows that
+fell back in one call are reported with each gpu_sync side. The sides
+alternate in
 one process after a warm-up; each is reported as seconds per batch, median
 and spread (min..max) over --reps timed calls. Prints one JSON line per
 result and, with --md, appends a markdown table. Needs a GPU: there is no
@@ -59,6 +69,8 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--quality", type=int, default=90)
     ap.add_argument("--md", help="append a markdown table to this file")
+    ap.add_argument("--sets", help="comma-separated file sets to run "
+                    "(default: all)")
     args = ap.parse_args()
     if args.reps < 5:
         ap.error("--reps must be >= 5")
@@ -77,20 +89,38 @@ def main():
                                 subsampling=2, restart_marker_rows=1)
         pil.append(buf.getvalue())
     sets["pillow420_rows1_smooth"] = pil
+    for clip in ("smooth", "noise"):
+        plain = []
+        for f in frames(clip, args.batch):
+            buf = io.BytesIO()
+            Image.fromarray(f).save(buf, "JPEG", quality=args.quality,
+                                    subsampling=2)
+            plain.append(buf.getvalue())
+        sets["pillow420_plain_" + clip] = plain
+    if args.sets:
+        sets = {k: sets[k] for k in args.sets.split(",")}
 
     rows = []
     sync = {}  # per gpu mode: seconds waited in the call's synchronise
-    modes = ("gpu", "cpu", "pillow")
+    sync_chunks = {"gpu_sync": 0, "gpu_sync_32": 32, "gpu_sync_64": 64,
+                   "gpu_sync_128": 128, "gpu_sync_256": 256}
 
     def run(mode, blobs):
         if mode == "pillow":
             return pillow_side(blobs)
-        s = _core.jpeg_decode_bench(blobs, 1, mode)[0]
-        if mode == "gpu":
+        if mode in sync_chunks:
+            s = _core.jpeg_decode_bench(blobs, 1, "gpu", serial_scan="device",
+                                        chunk_bytes=sync_chunks[mode])[0]
+        else:
+            s = _core.jpeg_decode_bench(blobs, 1, mode)[0]
+        if mode.startswith("gpu"):
             sync[mode].append(_core.jpeg_decode_last_sync_seconds())
         return s
 
     for name, blobs in sets.items():
+        plain = _core.jpeg_decode_info(blobs[0])["restart_interval"] == 0
+        modes = ("gpu",) + (tuple(sync_chunks) if plain else ()) + \
+            ("cpu", "pillow")
         secs = {m: [] for m in modes}
         sync.clear()
         sync.update({m: [] for m in modes})
@@ -111,14 +141,26 @@ def main():
                  "frames_per_s": args.batch / med}
             if sync[m]:  # warm-up call included; the median ignores it
                 r["sync_wait_seconds_median"] = statistics.median(sync[m])
+            if m in sync_chunks:
+                st = _core.jpeg_sync_model(blobs[0], sync_chunks[m])[1]
+                r["chunk_bytes"] = sync_chunks[m] or \
+                    _core.jpeg_sync_chunk_bytes()
+                r["model_first_file"] = {
+                    k: st[k] for k in ("chunks", "groups", "group_iterations",
+                                       "cross_rounds", "cross_repairs")}
+                r["fallback_rows"] = _core.jpeg_gpu_decode(
+                    blobs, serial_scan="device", chunk_bytes=sync_chunks[m],
+                    stats=True)[1]["fallback_rows"]
             rows.append(r)
             print(json.dumps(r), flush=True)
     _core.destroy_memory()
     if args.md:
         with open(args.md, "a") as f:
             f.write("| files | side | median ms/batch | min..max ms | frames/s "
-                    "| segments/file | bytes/file | sync wait ms |\n"
-                    "|---|---|---|---|---|---|---|---|\n")
+                    "| segments/file | bytes/file | sync wait ms | chunks, "
+                    "groups, in-group iterations, rounds used (first file) "
+                    "| fallback rows |\n"
+                    "|---|---|---|---|---|---|---|---|---|---|\n")
             for r in rows:
                 s = {k: v * 1e3 for k, v in r["seconds"].items()}
                 f.write(f"| {r['files']} | {r['mode']} | {s['median']:.3f} | "
@@ -127,6 +169,11 @@ def main():
                         f"| {r['bytes_per_file']} | "
                         + (f"{r['sync_wait_seconds_median'] * 1e3:.3f}"
                            if "sync_wait_seconds_median" in r else "")
+                        + " | "
+                        + (", ".join(str(r["model_first_file"][k]) for k in (
+                            "chunks", "groups", "group_iterations",
+                            "cross_rounds")) + f" | {r['fallback_rows']}"
+                           if "model_first_file" in r else " | ")
                         + " |\n")
 
 

@@ -28,6 +28,7 @@ CPP_SOURCES = [
     "csrc/ops/image_encoder.cpp",
     "csrc/ops/jpeg_cpu.cpp",
     "csrc/ops/jpeg_decode_cpu.cpp",
+    "csrc/ops/jpeg_sync_cpu.cpp",
     "csrc/ops/png_decode.cpp",
     "csrc/ops/image_decoder.cpp",
     "csrc/ops/detector.cpp",
@@ -47,6 +48,7 @@ HIP_SOURCES = [
     "kernels/svc_encode.hip",
     "kernels/jpeg_encode.hip",
     "kernels/jpeg_decode.hip",
+    "kernels/jpeg_sync_decode.hip",
     "kernels/color.hip",
     "kernels/optflow.hip",
     "kernels/gemm_mfma.hip",

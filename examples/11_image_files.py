@@ -57,7 +57,10 @@ img = sc.sources.Files(paths)
 # the GPU (camera, browser and default Pillow files); the default is "host"
 frame = sc.ops.ImageDecoder(img=img, serial_scan="device", device=dev)
 thumb = sc.ops.Resize(frame=frame, width=64, height=48, device=dev)
-out = sc.ops.ImageEncoder(frame=thumb, format="jpg", quality=85, device=dev)
+# subsampling="420" halves the chroma resolution, as cameras and browsers
+# do: smaller files, same bytes on both devices (the default is "444")
+out = sc.ops.ImageEncoder(frame=thumb, format="jpg", quality=85,
+                          subsampling="420", device=dev)
 thumbs = os.path.join(tmp, "thumbs")
 os.makedirs(thumbs)
 prof = sc.run(sc.sinks.Files(out, thumbs, ext="jpg"),
@@ -76,6 +79,9 @@ err = np.abs(first.astype(int) - frames[0].astype(int)).mean()
 small = _core.image_cpu_decode(
     open(os.path.join(thumbs, "c0_0.jpg"), "rb").read())
 assert small.shape == (48, 64, 3)
+thumb_info = _core.jpeg_decode_info(
+    open(os.path.join(thumbs, "c0_0.jpg"), "rb").read())
+assert (thumb_info["hs"], thumb_info["vs"]) == (2, 2)
 print(f"decoded {len(paths)} stills on the {'GPU' if gpu else 'CPU'} "
       f"(mean abs error of the round trip {err:.2f}), wrote "
       f"{len(written)} thumbnails")

@@ -833,35 +833,73 @@ PYBIND11_MODULE(_core, m) {
         py::arg("iters") = 1, py::arg("mode") = "gpu",
         py::arg("clip") = "smooth", py::arg("seed") = 0);
   // ---- JPEG still-image encode (ops/jpeg_cpu.cpp, kernels/jpeg_encode.hip)
-  m.def("jpeg_restart_interval", []() { return kJpegRestartInterval; });
-  m.def("jpeg_size_bound", &jpeg_size_bound, py::arg("h"), py::arg("w"),
-        py::arg("c"));
+  // every binding below takes subsampling = "444" | "420" last
+  m.def("jpeg_restart_interval",
+        [](const std::string& subsampling) {
+          return jpeg_parse_subsampling(subsampling) == JpegSubsampling::k420
+                     ? kJpegRestartInterval420
+                     : kJpegRestartInterval;
+        },
+        py::arg("subsampling") = "444");
+  m.def("jpeg_size_bound",
+        [](i32 h, i32 w, i32 c, const std::string& subsampling) {
+          return jpeg_size_bound(h, w, c, jpeg_parse_subsampling(subsampling));
+        },
+        py::arg("h"), py::arg("w"), py::arg("c"),
+        py::arg("subsampling") = "444");
   // the oracle: one [H,W,C] u8 frame -> file bytes
   m.def("jpeg_cpu_encode",
         [](py::array_t<u8, py::array::c_style | py::array::forcecast> frame,
-           i32 quality) {
+           i32 quality, const std::string& subsampling) {
           SCA_CHECK(frame.ndim() == 3, "frame must be [H,W,C]");
           auto v = jpeg_encode_cpu(frame.data(), (i32)frame.shape(0),
                                    (i32)frame.shape(1), (i32)frame.shape(2),
-                                   quality);
+                                   quality,
+                                   jpeg_parse_subsampling(subsampling));
           return py::bytes((const char*)v.data(), v.size());
         },
-        py::arg("frame"), py::arg("quality") = 90);
-  // quantised coefficients, int16 [ncomp, by, bx, 64] in zig-zag order
+        py::arg("frame"), py::arg("quality") = 90,
+        py::arg("subsampling") = "444");
+  // quantised coefficients, int16 [ncomp, by, bx, 64] in zig-zag order. A
+  // 3-channel frame with subsampling="420" gives a tuple of two arrays on
+  // their own block grids: Y [2*mcus_y, 2*mcus_x, 64] and chroma
+  // [2, mcus_y, mcus_x, 64] (Cb, Cr), mcus_* counting 16x16-pixel MCUs.
   m.def("jpeg_quantize_cpu",
         [](py::array_t<u8, py::array::c_style | py::array::forcecast> frame,
-           i32 quality) {
+           i32 quality, const std::string& subsampling) -> py::object {
           SCA_CHECK(frame.ndim() == 3, "frame must be [H,W,C]");
           i32 h = (i32)frame.shape(0), w = (i32)frame.shape(1),
               c = (i32)frame.shape(2);
           jpeg_check_args(h, w, c, quality);
           JpegTables t;
           jpeg_make_tables(c, quality, t);
-          JpegGeom g = jpeg_geom(h, w, c);
+          JpegGeom g =
+              jpeg_geom(h, w, c, jpeg_parse_subsampling(subsampling));
+          i16 zz[64];
+          if (g.ss == JpegSubsampling::k420) {
+            py::array_t<i16> ya(
+                {(i64)g.mcus_y * 2, (i64)g.mcus_x * 2, (i64)64});
+            py::array_t<i16> ca(
+                {(i64)2, (i64)g.mcus_y, (i64)g.mcus_x, (i64)64});
+            i16* o = ya.mutable_data();
+            for (u32 by = 0; by < g.mcus_y * 2; ++by)
+              for (u32 bx = 0; bx < g.mcus_x * 2; ++bx, o += 64) {
+                jpeg_block_coefs(frame.data(), h, w, c, bx, by, 0, t, zz);
+                std::memcpy(o, zz, sizeof(zz));
+              }
+            o = ca.mutable_data();
+            for (i32 comp = 1; comp < 3; ++comp)
+              for (u32 by = 0; by < g.mcus_y; ++by)
+                for (u32 bx = 0; bx < g.mcus_x; ++bx, o += 64) {
+                  jpeg_block_coefs_420(frame.data(), h, w, bx, by, comp, t,
+                                       zz);
+                  std::memcpy(o, zz, sizeof(zz));
+                }
+            return py::make_tuple(ya, ca);
+          }
           py::array_t<i16> out(
               {(i64)c, (i64)g.mcus_y, (i64)g.mcus_x, (i64)64});
           i16* o = out.mutable_data();
-          i16 zz[64];
           for (i32 comp = 0; comp < c; ++comp)
             for (u32 by = 0; by < g.mcus_y; ++by)
               for (u32 bx = 0; bx < g.mcus_x; ++bx, o += 64) {
@@ -870,13 +908,15 @@ PYBIND11_MODULE(_core, m) {
               }
           return out;
         },
-        py::arg("frame"), py::arg("quality") = 90);
+        py::arg("frame"), py::arg("quality") = 90,
+        py::arg("subsampling") = "444");
   // [N,H,W,C] u8 frames are uploaded as ONE contiguous device buffer (frame
   // i at i*H*W*C, so an odd frame size gives misaligned frames) and encoded
   // in one call -> list of file bytes
   m.def("jpeg_gpu_encode",
         [](py::array_t<u8, py::array::c_style | py::array::forcecast> frames,
-           i32 quality) {
+           i32 quality, const std::string& subsampling) {
+          JpegSubsampling ss = jpeg_parse_subsampling(subsampling);
           SCA_CHECK(have_gpu(), "jpeg_gpu_encode needs a GPU");
           SCA_CHECK(frames.ndim() == 4, "frames must be [N,H,W,C]");
           i64 n = frames.shape(0);
@@ -895,7 +935,7 @@ PYBIND11_MODULE(_core, m) {
             std::vector<const u8*> fp;
             for (i64 i = 0; i < n; ++i) fp.push_back(d + (size_t)i * fsize);
             jpeg_encode_gpu(fp, h, w, c, quality, dev, per_thread_hip_stream(),
-                            bufs, sizes);
+                            bufs, sizes, ss);
             for (size_t i = 0; i < bufs.size(); ++i) {
               std::string host(sizes[i], '\0');
               memcpy_buffer((u8*)host.data(), CPU_DEVICE, bufs[i], dev,
@@ -911,16 +951,20 @@ PYBIND11_MODULE(_core, m) {
           delete_buffer(dev, d);
           return res;
         },
-        py::arg("frames"), py::arg("quality") = 90);
+        py::arg("frames"), py::arg("quality") = 90,
+        py::arg("subsampling") = "444");
   // Seconds for `iters` encodes of `batch` device-resident h*w*c frames,
   // each ending with the files in host memory. mode "gpu": jpeg_encode_gpu,
   // then D2H of the compressed bytes. mode "cpu": D2H of the raw frames,
   // then jpeg_encode_cpu. mode "png": D2H of the raw frames, then the PNG
   // writer (the only image path before the JPEG encoder). Also returns the
   // bytes produced by one iteration. clip: "smooth" gradients or "noise".
+  // subsampling applies to the two JPEG modes.
   m.def("jpeg_encode_bench",
         [](i32 h, i32 w, i32 c, i32 quality, i64 batch, i32 iters,
-           const std::string& mode, const std::string& clip) {
+           const std::string& mode, const std::string& clip,
+           const std::string& subsampling) {
+          JpegSubsampling ss = jpeg_parse_subsampling(subsampling);
           SCA_CHECK(have_gpu(), "jpeg_encode_bench needs a GPU");
           SCA_CHECK(mode == "gpu" || mode == "cpu" || mode == "png",
                     "mode must be 'gpu', 'cpu' or 'png'");
@@ -964,7 +1008,7 @@ PYBIND11_MODULE(_core, m) {
                 std::vector<u8*> bufs;
                 std::vector<u64> sizes;
                 jpeg_encode_gpu(fp, h, w, c, quality, dev,
-                                per_thread_hip_stream(), bufs, sizes);
+                                per_thread_hip_stream(), bufs, sizes, ss);
                 std::vector<u8*> dst;
                 std::vector<const u8*> src(bufs.begin(), bufs.end());
                 std::vector<size_t> sz(sizes.begin(), sizes.end());
@@ -983,7 +1027,7 @@ PYBIND11_MODULE(_core, m) {
                 memcpy_vec(dst, CPU_DEVICE, fp, dev, sz);
                 for (i64 i = 0; i < batch; ++i) {
                   auto v = mode == "cpu"
-                               ? jpeg_encode_cpu(dst[i], h, w, c, quality)
+                               ? jpeg_encode_cpu(dst[i], h, w, c, quality, ss)
                                : encode_png(dst[i], h, w, c);
                   out_bytes += v.size();
                   delete_buffer(CPU_DEVICE, dst[i]);
@@ -1002,7 +1046,7 @@ PYBIND11_MODULE(_core, m) {
         },
         py::arg("h"), py::arg("w"), py::arg("c"), py::arg("quality") = 90,
         py::arg("batch") = 8, py::arg("iters") = 1, py::arg("mode") = "gpu",
-        py::arg("clip") = "smooth");
+        py::arg("clip") = "smooth", py::arg("subsampling") = "444");
   // ---- still-image decode (ops/jpeg_decode_cpu.cpp, ops/png_decode.cpp,
   // kernels/jpeg_decode.hip)
   auto image_to_array = [](const DecodedImage& img) {

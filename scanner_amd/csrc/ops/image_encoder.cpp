@@ -88,6 +88,9 @@ class ImageEncoderKernelCPU : public BatchedKernel {
     SCA_CHECK(format_ == "png" || (quality_ >= 1 && quality_ <= 100),
               "ImageEncoder quality must be in 1..100, got " +
                   std::to_string(quality_));
+    // like quality, read for JPEG only
+    if (format_ != "png")
+      subsampling_ = jpeg_parse_subsampling(a.get_str("subsampling", "444"));
   }
   void execute_batch(const BatchedElements& in, BatchedElements& out) override {
     for (const Element& f : in[0]) {
@@ -97,7 +100,8 @@ class ImageEncoderKernelCPU : public BatchedKernel {
           c = f.frame_info.shape[2];
       auto blob = format_ == "png"
                       ? encode_png(f.buffer, h, w, c)
-                      : jpeg_encode_cpu(f.buffer, h, w, c, quality_);
+                      : jpeg_encode_cpu(f.buffer, h, w, c, quality_,
+                                        subsampling_);
       Element e;
       e.size = blob.size();
       e.buffer = new_buffer(config_.device, e.size);
@@ -110,6 +114,7 @@ class ImageEncoderKernelCPU : public BatchedKernel {
  private:
   std::string format_;
   i32 quality_;
+  JpegSubsampling subsampling_ = JpegSubsampling::k444;
 };
 
 }  // namespace

@@ -12,6 +12,21 @@
 //   starts from DC prediction 0, is padded to a byte with 1-bits and is
 //   byte-stuffed on its own; segments are separated by RST(n mod 8).
 //
+// 4:2:0 mode (JpegSubsampling::k420, 3 channels only; a 1-channel frame has
+// no chroma and is written exactly as in 4:4:4):
+//   SOF0 sampling factors Y 2x2, Cb 1x1, Cr 1x1. One MCU is 16x16 pixels and
+//   6 blocks in the order Y(0,0) Y(0,1) Y(1,0) Y(1,1) Cb Cr (T.81 A.2.3).
+//   The restart interval is kJpegRestartInterval420 = 16 MCUs, 96 blocks, the
+//   block count of a 4:4:4 segment; DRI carries 16. DC prediction is per
+//   component and starts from 0 in each segment; Y chains through the four Y
+//   blocks of an MCU and on into the next MCU. Pixel coordinates past the
+//   right or bottom edge clamp to w-1 / h-1 before anything else, so a 1x1
+//   image is one MCU of one replicated pixel. A chroma sample is the 2x2 box
+//   mean jpeg_downsample4 of the Q4 samples jpeg_sample_rgb returns for the
+//   four (clamped) pixels: (a + b + c + d + 2) >> 2, arithmetic shift, with
+//   no 8-bit rounding of Cb/Cr before it. DCT, quantisation and entropy
+//   coding are those of 4:4:4.
+//
 // Fixed-point pipeline of one 8x8 block:
 //   sample  Q4   level-shifted component value (pixel - 128) * 16
 //   row DCT Q4 * Q14 constants -> descaled to Q6 (fits int16)
@@ -34,7 +49,9 @@
 
 namespace sca {
 
-constexpr i32 kJpegRestartInterval = 32;  // MCUs per restart segment
+constexpr i32 kJpegRestartInterval = 32;     // MCUs per 4:4:4 segment
+constexpr i32 kJpegRestartInterval420 = 16;  // MCUs per 4:2:0 segment
+enum class JpegSubsampling : i32 { k444 = 0, k420 = 1 };
 // Longest code of one block: DC 9 + 11 bits, 63 x (AC 16 + 10 bits) = 1658
 // bits -> 208 bytes; every byte can be 0xFF and need a stuffed zero.
 constexpr u32 kJpegBlockMaxBytes = 208;
@@ -64,6 +81,10 @@ JPEG_HD inline i32 jpeg_sample_rgb(i32 r, i32 g, i32 b, int comp) {
   return (v + 2048) >> 12;
 }
 JPEG_HD inline i32 jpeg_sample_grey(i32 y) { return (y - 128) * 16; }
+// 4:2:0 chroma sample: box mean of the Q4 samples of one 2x2 pixel cell
+JPEG_HD inline i32 jpeg_downsample4(i32 a, i32 b, i32 c, i32 d) {
+  return (a + b + c + d + 2) >> 2;
+}
 
 // ---- 8-point DCT-II, orthonormal, constants in Q14 ----
 // out[u] = sum_x in[x] * c(u)/2 * cos((2x+1) u pi / 16), not descaled.
@@ -141,33 +162,55 @@ struct JpegGeom {
   i32 h, w, c;
   u32 mcus_x, mcus_y, nmcu, nseg;
   u32 seg_stride;  // worst-case bytes of one stuffed restart segment
+  u32 mcu_px;      // MCU width and height in pixels: 8, or 16 in 4:2:0
+  u32 mcu_blocks;  // blocks per MCU: c, or 6 in 4:2:0
+  u32 restart;     // MCUs per restart segment
+  JpegSubsampling ss;  // the mode in effect: k444 for every 1-channel frame
 };
-JPEG_HD inline JpegGeom jpeg_geom(i32 h, i32 w, i32 c) {
+JPEG_HD inline JpegGeom jpeg_geom(
+    i32 h, i32 w, i32 c, JpegSubsampling ss = JpegSubsampling::k444) {
   JpegGeom g;
   g.h = h;
   g.w = w;
   g.c = c;
-  g.mcus_x = ((u32)w + 7) / 8;
-  g.mcus_y = ((u32)h + 7) / 8;
+  bool sub = ss == JpegSubsampling::k420 && c == 3;
+  g.ss = sub ? JpegSubsampling::k420 : JpegSubsampling::k444;
+  g.mcu_px = sub ? 16 : 8;
+  g.mcu_blocks = sub ? 6 : (u32)c;
+  g.restart = (u32)(sub ? kJpegRestartInterval420 : kJpegRestartInterval);
+  g.mcus_x = ((u32)w + g.mcu_px - 1) / g.mcu_px;
+  g.mcus_y = ((u32)h + g.mcu_px - 1) / g.mcu_px;
   g.nmcu = g.mcus_x * g.mcus_y;
-  g.nseg = (g.nmcu + kJpegRestartInterval - 1) / kJpegRestartInterval;
-  g.seg_stride = kJpegRestartInterval * (u32)c * kJpegBlockMaxStuffed;
+  g.nseg = (g.nmcu + g.restart - 1) / g.restart;
+  g.seg_stride = g.restart * g.mcu_blocks * kJpegBlockMaxStuffed;
   return g;
 }
 
 // ---- host API (jpeg_cpu.cpp) ----
 void jpeg_make_tables(i32 c, i32 quality, JpegTables& t);
-// SOI .. SOS, the same for every frame of one shape and quality
-std::vector<u8> jpeg_header(i32 h, i32 w, i32 c, const JpegTables& t);
+// "444" | "420" -> mode; anything else (4:2:2 included) is an error that
+// lists the supported values
+JpegSubsampling jpeg_parse_subsampling(const std::string& name);
+// SOI .. SOS, the same for every frame of one shape, quality and mode
+std::vector<u8> jpeg_header(i32 h, i32 w, i32 c, const JpegTables& t,
+                            JpegSubsampling ss = JpegSubsampling::k444);
 // Header, worst-case entropy bytes (stuffing included), restart markers
 // and EOI: no h x w x c frame encodes to more.
-u64 jpeg_size_bound(i32 h, i32 w, i32 c);
-// Quantised coefficients of component `comp` of block (bx, by), zig-zag
-// order; pixels past the right/bottom edge replicate the last column/row.
+u64 jpeg_size_bound(i32 h, i32 w, i32 c,
+                    JpegSubsampling ss = JpegSubsampling::k444);
+// Quantised coefficients of component `comp` of block (bx, by) of the
+// full-resolution 8x8 block grid, zig-zag order; pixels past the
+// right/bottom edge replicate the last column/row. The Y blocks of a 4:2:0
+// file are these too: MCU (mx, my) holds blocks (2mx + j, 2my + i).
 void jpeg_block_coefs(const u8* pix, i32 h, i32 w, i32 c, u32 bx, u32 by,
                       int comp, const JpegTables& t, i16 (&zz)[64]);
+// The same for a 4:2:0 chroma block: (bx, by) counts blocks of 8x8 chroma
+// samples, i.e. 16x16 pixels; comp is 1 (Cb) or 2 (Cr); 3-channel frames.
+void jpeg_block_coefs_420(const u8* pix, i32 h, i32 w, u32 bx, u32 by,
+                          int comp, const JpegTables& t, i16 (&zz)[64]);
 std::vector<u8> jpeg_encode_cpu(const u8* pix, i32 h, i32 w, i32 c,
-                                i32 quality);
+                                i32 quality,
+                                JpegSubsampling ss = JpegSubsampling::k444);
 void jpeg_check_args(i32 h, i32 w, i32 c, i32 quality);
 
 // ---- HIP encoder (kernels/jpeg_encode.hip) ----
@@ -177,6 +220,7 @@ void jpeg_check_args(i32 h, i32 w, i32 c, i32 quality);
 // delete_buffer(dev, out[i]). Everything is issued on `stream`.
 void jpeg_encode_gpu(const std::vector<const u8*>& frames, i32 h, i32 w,
                      i32 c, i32 quality, DeviceHandle dev, void* stream,
-                     std::vector<u8*>& out, std::vector<u64>& sizes);
+                     std::vector<u8*>& out, std::vector<u64>& sizes,
+                     JpegSubsampling ss = JpegSubsampling::k444);
 
 }  // namespace sca

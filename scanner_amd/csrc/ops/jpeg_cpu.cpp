@@ -139,7 +139,16 @@ void jpeg_make_tables(i32 c, i32 quality, JpegTables& t) {
   }
 }
 
-std::vector<u8> jpeg_header(i32 h, i32 w, i32 c, const JpegTables& t) {
+JpegSubsampling jpeg_parse_subsampling(const std::string& name) {
+  if (name == "444") return JpegSubsampling::k444;
+  if (name == "420") return JpegSubsampling::k420;
+  throw ScannerError("JPEG subsampling must be one of '444', '420', got '" +
+                     name + "'");
+}
+
+std::vector<u8> jpeg_header(i32 h, i32 w, i32 c, const JpegTables& t,
+                            JpegSubsampling ss) {
+  JpegGeom g = jpeg_geom(h, w, c, ss);
   int ntab = c == 3 ? 2 : 1;
   std::vector<u8> v;
   put16(v, 0xffd8);  // SOI
@@ -161,7 +170,8 @@ std::vector<u8> jpeg_header(i32 h, i32 w, i32 c, const JpegTables& t) {
   v.push_back((u8)c);
   for (int i = 0; i < c; ++i) {
     v.push_back((u8)(i + 1));      // component id
-    v.push_back(0x11);             // 1x1 sampling
+    // sampling factors: 1x1, or 2x2 for the Y of a 4:2:0 file
+    v.push_back(i == 0 && g.ss == JpegSubsampling::k420 ? 0x22 : 0x11);
     v.push_back(i == 0 ? 0 : 1);   // quantisation table
   }
   for (int k = 0; k < ntab; ++k) {
@@ -170,7 +180,7 @@ std::vector<u8> jpeg_header(i32 h, i32 w, i32 c, const JpegTables& t) {
   }
   put16(v, 0xffdd);  // DRI
   put16(v, 4);
-  put16(v, (u32)kJpegRestartInterval);
+  put16(v, g.restart);
   put16(v, 0xffda);  // SOS
   put16(v, 6 + 2 * c);
   v.push_back((u8)c);
@@ -184,15 +194,34 @@ std::vector<u8> jpeg_header(i32 h, i32 w, i32 c, const JpegTables& t) {
   return v;
 }
 
-u64 jpeg_size_bound(i32 h, i32 w, i32 c) {
+u64 jpeg_size_bound(i32 h, i32 w, i32 c, JpegSubsampling ss) {
   jpeg_check_args(h, w, c, 50);
   JpegTables t;
   jpeg_make_tables(c, 50, t);
-  JpegGeom g = jpeg_geom(h, w, c);
+  JpegGeom g = jpeg_geom(h, w, c, ss);
   // every segment is followed by a 2-byte marker (RSTn or EOI)
-  return jpeg_header(h, w, c, t).size() +
-         (u64)g.nmcu * c * kJpegBlockMaxStuffed + 2ull * g.nseg;
+  return jpeg_header(h, w, c, t, ss).size() +
+         (u64)g.nmcu * g.mcu_blocks * kJpegBlockMaxStuffed + 2ull * g.nseg;
 }
+
+namespace {
+
+// row-pass results (Q6) -> column DCT, quantisation, zig-zag
+void column_pass(const i32 (&rows)[8][8], int comp, const JpegTables& t,
+                 i16 (&zz)[64]) {
+  const u16* q = t.q[comp ? 1 : 0];
+  for (int u = 0; u < 8; ++u) {
+    i32 in[8], out[8];
+    for (int r = 0; r < 8; ++r) in[r] = rows[r][u];
+    jpeg_dct8(in, out);
+    for (int v = 0; v < 8; ++v) {
+      int nat = v * 8 + u;
+      zz[t.nat2zz[nat]] = (i16)jpeg_quantize(out[v], q[nat]);
+    }
+  }
+}
+
+}  // namespace
 
 void jpeg_block_coefs(const u8* pix, i32 h, i32 w, i32 c, u32 bx, u32 by,
                       int comp, const JpegTables& t, i16 (&zz)[64]) {
@@ -209,34 +238,64 @@ void jpeg_block_coefs(const u8* pix, i32 h, i32 w, i32 c, u32 bx, u32 by,
     jpeg_dct8(in, out);
     for (int u = 0; u < 8; ++u) rows[r][u] = jpeg_descale_row(out[u]);
   }
-  const u16* q = t.q[comp ? 1 : 0];
-  for (int u = 0; u < 8; ++u) {
+  column_pass(rows, comp, t, zz);
+}
+
+void jpeg_block_coefs_420(const u8* pix, i32 h, i32 w, u32 bx, u32 by,
+                          int comp, const JpegTables& t, i16 (&zz)[64]) {
+  i32 rows[8][8];
+  for (int r = 0; r < 8; ++r) {
+    i32 y0 = std::min<i32>(((i32)by * 8 + r) * 2, h - 1);
+    i32 y1 = std::min<i32>(((i32)by * 8 + r) * 2 + 1, h - 1);
     i32 in[8], out[8];
-    for (int r = 0; r < 8; ++r) in[r] = rows[r][u];
-    jpeg_dct8(in, out);
-    for (int v = 0; v < 8; ++v) {
-      int nat = v * 8 + u;
-      zz[t.nat2zz[nat]] = (i16)jpeg_quantize(out[v], q[nat]);
+    for (int k = 0; k < 8; ++k) {
+      i32 x0 = std::min<i32>(((i32)bx * 8 + k) * 2, w - 1);
+      i32 x1 = std::min<i32>(((i32)bx * 8 + k) * 2 + 1, w - 1);
+      auto sample = [&](i32 y, i32 x) {
+        const u8* p = pix + ((size_t)y * w + x) * 3;
+        return jpeg_sample_rgb(p[0], p[1], p[2], comp);
+      };
+      in[k] = jpeg_downsample4(sample(y0, x0), sample(y0, x1), sample(y1, x0),
+                               sample(y1, x1));
     }
+    jpeg_dct8(in, out);
+    for (int u = 0; u < 8; ++u) rows[r][u] = jpeg_descale_row(out[u]);
   }
+  column_pass(rows, comp, t, zz);
 }
 
 std::vector<u8> jpeg_encode_cpu(const u8* pix, i32 h, i32 w, i32 c,
-                                i32 quality) {
+                                i32 quality, JpegSubsampling ss) {
   jpeg_check_args(h, w, c, quality);
   JpegTables t;
   jpeg_make_tables(c, quality, t);
-  JpegGeom g = jpeg_geom(h, w, c);
-  std::vector<u8> out = jpeg_header(h, w, c, t);
+  JpegGeom g = jpeg_geom(h, w, c, ss);
+  std::vector<u8> out = jpeg_header(h, w, c, t, ss);
   i16 zz[64];
   for (u32 s = 0; s < g.nseg; ++s) {
     BitWriter bw{out};
     i32 pred[3] = {0, 0, 0};
-    u32 m1 = std::min<u32>(g.nmcu, (s + 1) * kJpegRestartInterval);
-    for (u32 m = s * kJpegRestartInterval; m < m1; ++m) {
+    u32 m1 = std::min<u32>(g.nmcu, (s + 1) * g.restart);
+    for (u32 m = s * g.restart; m < m1; ++m) {
+      u32 mx = m % g.mcus_x, my = m / g.mcus_x;
+      if (g.ss == JpegSubsampling::k420) {
+        // Y(0,0) Y(0,1) Y(1,0) Y(1,1) Cb Cr
+        for (u32 k = 0; k < 6; ++k) {
+          int comp = k < 4 ? 0 : (int)k - 3;
+          if (k < 4) {
+            jpeg_block_coefs(pix, h, w, c, 2 * mx + (k & 1), 2 * my + (k >> 1),
+                             0, t, zz);
+          } else {
+            jpeg_block_coefs_420(pix, h, w, mx, my, comp, t, zz);
+          }
+          int tab = comp ? 1 : 0;
+          jpeg_code_block(zz, pred[comp], t.dc[tab], t.ac[tab], bw);
+          pred[comp] = zz[0];
+        }
+        continue;
+      }
       for (int comp = 0; comp < c; ++comp) {
-        jpeg_block_coefs(pix, h, w, c, m % g.mcus_x, m / g.mcus_x, comp, t,
-                         zz);
+        jpeg_block_coefs(pix, h, w, c, mx, my, comp, t, zz);
         int k = comp ? 1 : 0;
         jpeg_code_block(zz, pred[comp], t.dc[k], t.ac[k], bw);
         pred[comp] = zz[0];

@@ -19,6 +19,18 @@
 //                 with a ballot prefix and stored to the segment's slot in
 //                 device staging (worst-case stride); byte count -> sizes
 //            Coefficients never reach global memory.
+//            4:2:0 (S420): the segment is 16 MCUs of 16x16 pixels, again
+//            96 blocks, block b = MCU * 6 + {Y00, Y01, Y10, Y11, Cb, Cr}:
+//              A  lane (pixel row r of 16, MCU m of 16), tid = r * 16 + m,
+//                 loads 16 pixels of one row, runs the two Y row DCTs and
+//                 pair-sums Cb/Cr horizontally; the sums of row r ^ 1 come
+//                 from 16 lanes away in the same wave by a shuffle, and the
+//                 even-row lane rounds (jpeg_downsample4) and runs the
+//                 chroma row DCTs of chroma row r / 2
+//              B  lane (u, MCU m) x 3 steps covers block kinds 2 per step
+//              C  the DC predictor of a block is the previous block of its
+//                 component: b-1 (Y01..Y11), b-3 (Y00), b-6 (Cb, Cr)
+//              D  as above
 //   scan     one workgroup per frame: exclusive scan of (segment size + 2
 //            marker bytes) for any segment count -> offsets and file size.
 //   gather   grid (segments, frames): header, compacted segments, RSTn
@@ -51,6 +63,11 @@ namespace {
 constexpr u32 kR = kJpegRestartInterval;
 constexpr u32 kThreads = 256;
 static_assert(kR * 8 == kThreads, "one lane per (MCU, row) of a segment");
+constexpr u32 kR420 = kJpegRestartInterval420;
+static_assert(kR420 * 16 == kThreads, "one lane per (MCU, row) in 4:2:0");
+static_assert(kR420 * 6 == kR * 3, "both modes code 96 blocks per segment");
+static_assert(64 % kR420 == 0 && (64 / kR420) % 2 == 0,
+              "rows r and r ^ 1 of an MCU sit in one wave");
 constexpr u32 kMaxChunk = 16;  // frames per launch sequence
 // staging holds worst-case segments (about 7x the raw frame); frames per
 // launch sequence are limited so that it stays below this
@@ -118,21 +135,21 @@ struct BitMerge {
   }
 };
 
-// 8 pixels of one row, C bytes each, starting at column x0 of `row`
-template <int C>
+// N (8 or 16) pixels of one row, C bytes each, starting at column x0 of `row`
+template <int C, int N = 8>
 __device__ inline void load_pixels(const u8* __restrict__ row, u32 x0, i32 w,
-                                   u8 (&px)[8 * C]) {
+                                   u8 (&px)[N * C]) {
   const u8* p = row + (u64)x0 * C;
-  if (x0 + 8 <= (u32)w && ((uintptr_t)p & 3) == 0) {
+  if (x0 + N <= (u32)w && ((uintptr_t)p & 3) == 0) {
     const u32* p4 = reinterpret_cast<const u32*>(p);
-    u32 v[2 * C];
+    u32 v[N * C / 4];
 #pragma unroll
-    for (int k = 0; k < 2 * C; ++k) v[k] = p4[k];
+    for (int k = 0; k < N * C / 4; ++k) v[k] = p4[k];
 #pragma unroll
-    for (int k = 0; k < 8 * C; ++k) px[k] = (u8)(v[k / 4] >> (8 * (k & 3)));
+    for (int k = 0; k < N * C; ++k) px[k] = (u8)(v[k / 4] >> (8 * (k & 3)));
   } else {
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
+    for (int k = 0; k < N; ++k) {
       u32 x = min(x0 + (u32)k, (u32)w - 1);  // replicate the last column
 #pragma unroll
       for (int ch = 0; ch < C; ++ch) px[k * C + ch] = row[(u64)x * C + ch];
@@ -140,17 +157,22 @@ __device__ inline void load_pixels(const u8* __restrict__ row, u32 x0, i32 w,
   }
 }
 
-template <int C>
+// S420: the 4:2:0 variant (C == 3), see the file comment
+template <int C, bool S420 = false>
 __global__ void __launch_bounds__(kThreads) jpeg_segment_kernel(JpegEncArgs a) {
+  static_assert(!S420 || C == 3, "4:2:0 needs three channels");
+  constexpr u32 R = S420 ? kR420 : kR;     // MCUs per segment
+  constexpr u32 MB = S420 ? 6u : (u32)C;   // blocks per MCU
+  static_assert(R * MB <= kR * 3, "LDS is sized for 96 blocks");
   __shared__ JpegTables t;
   __shared__ u32 bits[kBitWords];
-  __shared__ i16 coef[kR * C * kCoefStride];
+  __shared__ i16 coef[R * MB * kCoefStride];
   __shared__ u32 wave_sum[kThreads / 64];
   u32 s = blockIdx.x, f = blockIdx.y, tid = threadIdx.x;
   u32 lane = tid & 63, wave = tid >> 6;
   const JpegGeom& g = a.g;
-  u32 m0 = s * kR;
-  u32 nm = min(kR, g.nmcu - m0);  // MCUs in this segment
+  u32 m0 = s * R;
+  u32 nm = min(R, g.nmcu - m0);  // MCUs in this segment
 
   for (u32 i = tid; i < sizeof(JpegTables) / 4; i += kThreads)
     reinterpret_cast<u32*>(&t)[i] = reinterpret_cast<const u32*>(a.tables)[i];
@@ -158,7 +180,53 @@ __global__ void __launch_bounds__(kThreads) jpeg_segment_kernel(JpegEncArgs a) {
   // ---- A: load, colour, row DCT -> rowres[comp][r][m][u] (Q6); a lane
   // writes 16 contiguous bytes next to its neighbour's ----
   i16* rowres = reinterpret_cast<i16*>(bits);
-  {
+  if constexpr (S420) {
+    // rowres[kind][row of the block][m][u], kind = Y00 Y01 Y10 Y11 Cb Cr.
+    // m < nm is the same for the lanes of rows r and r ^ 1, and a clamped
+    // row only changes the address a lane loads from, so both partners of
+    // a shuffle are always active together.
+    u32 r = tid / R, m = tid % R;
+    if (m < nm) {
+      u32 mg = m0 + m;
+      u32 bx = mg % g.mcus_x, by = mg / g.mcus_x;
+      u32 y = min(by * 16 + r, (u32)g.h - 1);  // replicate the last row
+      u8 px[16 * 3];
+      load_pixels<3, 16>(a.frames[f] + (u64)y * g.w * 3, bx * 16, g.w, px);
+#pragma unroll
+      for (int half = 0; half < 2; ++half) {
+        i32 in[8], out[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          const u8* p = px + (half * 8 + k) * 3;
+          in[k] = jpeg_sample_rgb(p[0], p[1], p[2], 0);
+        }
+        jpeg_dct8(in, out);
+        i16* dst =
+            rowres + ((((r / 8) * 2 + half) * 8 + r % 8) * R + m) * 8;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) dst[u] = (i16)jpeg_descale_row(out[u]);
+      }
+#pragma unroll
+      for (int comp = 1; comp < 3; ++comp) {
+        i32 in[8], out[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          const u8* p = px + k * 6;
+          i32 sum = jpeg_sample_rgb(p[0], p[1], p[2], comp) +
+                    jpeg_sample_rgb(p[3], p[4], p[5], comp);
+          // the other row of the 2x2 cell; a + b + c + d + 2 >> 2 is
+          // jpeg_downsample4 whatever the order of the additions
+          in[k] = (sum + __shfl_xor(sum, (int)R, 64) + 2) >> 2;
+        }
+        if ((r & 1) == 0) {
+          jpeg_dct8(in, out);
+          i16* dst = rowres + (((3 + comp) * 8 + r / 2) * R + m) * 8;
+#pragma unroll
+          for (int u = 0; u < 8; ++u) dst[u] = (i16)jpeg_descale_row(out[u]);
+        }
+      }
+    }
+  } else {
     u32 r = tid / kR, m = tid % kR;
     if (m < nm) {
       u32 mg = m0 + m;
@@ -188,7 +256,28 @@ __global__ void __launch_bounds__(kThreads) jpeg_segment_kernel(JpegEncArgs a) {
   __syncthreads();
 
   // ---- B: column DCT, quantise, zig-zag -> coef[m * C + comp][64] ----
-  {
+  if constexpr (S420) {
+    u32 u = tid % 8;
+#pragma unroll
+    for (u32 j = 0; j < 3; ++j) {
+      u32 idx = j * 32 + tid / 8;  // kind * R + m, 0..95
+      u32 kind = idx / R, m = idx % R;
+      if (m < nm) {
+        const i16* src = rowres + (kind * 8 * R + m) * 8 + u;
+        i32 in[8], out[8];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) in[r] = src[r * R * 8];
+        jpeg_dct8(in, out);
+        const u16* q = t.q[kind < 4 ? 0 : 1];
+        i16* dst = coef + (m * 6 + kind) * kCoefStride;
+#pragma unroll
+        for (int v = 0; v < 8; ++v) {
+          u32 nat = v * 8 + u;
+          dst[t.nat2zz[nat]] = (i16)jpeg_quantize(out[v], q[nat]);
+        }
+      }
+    }
+  } else {
     u32 m = tid / 8, u = tid % 8;
     if (m < nm) {
 #pragma unroll
@@ -212,15 +301,19 @@ __global__ void __launch_bounds__(kThreads) jpeg_segment_kernel(JpegEncArgs a) {
 
   // ---- C: code lengths, scan, OR-merge into the zeroed bit image ----
   for (u32 i = tid; i < kBitWords; i += kThreads) bits[i] = 0;
-  u32 nb = nm * C;
+  u32 nb = nm * MB;
   const i16* zz = coef + tid * kCoefStride;
   i32 pred = 0;
-  u32 comp = tid % C;
-  const u32* dc = t.dc[comp ? 1 : 0];
-  const u32* ac = t.ac[comp ? 1 : 0];
+  u32 pos = tid % MB;  // position in the MCU
+  // blocks back to the previous one of the same component
+  u32 back = !S420 ? MB : pos >= 4 ? 6u : pos ? 1u : 3u;
+  bool chroma = S420 ? pos >= 4 : pos != 0;
+  const u32* dc = t.dc[chroma ? 1 : 0];
+  const u32* ac = t.ac[chroma ? 1 : 0];
   u32 my_bits = 0;
   if (tid < nb) {
-    if (tid >= (u32)C) pred = zz[-(i32)(C * kCoefStride)];  // previous MCU's DC
+    // the first block of a component in the segment predicts from 0
+    if (tid >= back) pred = zz[-(i32)(back * kCoefStride)];
     BitCount cnt;
     jpeg_code_block(zz, pred, dc, ac, cnt);
     my_bits = cnt.bits;
@@ -313,7 +406,8 @@ u64 align_up(u64 x, u64 a) { return (x + a - 1) / a * a; }
 
 void jpeg_encode_gpu(const std::vector<const u8*>& frames, i32 h, i32 w,
                      i32 c, i32 quality, DeviceHandle dev, void* stream,
-                     std::vector<u8*>& out, std::vector<u64>& sizes) {
+                     std::vector<u8*>& out, std::vector<u64>& sizes,
+                     JpegSubsampling ss) {
   jpeg_check_args(h, w, c, quality);
   SCA_CHECK(dev.is_gpu(), "jpeg_encode_gpu needs a GPU device");
   if (frames.empty()) return;
@@ -322,9 +416,9 @@ void jpeg_encode_gpu(const std::vector<const u8*>& frames, i32 h, i32 w,
 
   JpegTables tables;
   jpeg_make_tables(c, quality, tables);
-  std::vector<u8> header = jpeg_header(h, w, c, tables);
-  JpegGeom g = jpeg_geom(h, w, c);
-  u64 bound = jpeg_size_bound(h, w, c);
+  std::vector<u8> header = jpeg_header(h, w, c, tables, ss);
+  JpegGeom g = jpeg_geom(h, w, c, ss);
+  u64 bound = jpeg_size_bound(h, w, c, ss);
 
   u64 frame_staging = (u64)g.nseg * g.seg_stride;
   size_t chunk_max = (size_t)std::max<u64>(
@@ -362,7 +456,9 @@ void jpeg_encode_gpu(const std::vector<const u8*>& frames, i32 h, i32 w,
         a.frames[i] = frames[c0 + i];
       }
       dim3 grid(g.nseg, (u32)n);
-      if (c == 3) {
+      if (g.ss == JpegSubsampling::k420) {
+        jpeg_segment_kernel<3, true><<<grid, kThreads, 0, s>>>(a);
+      } else if (c == 3) {
         jpeg_segment_kernel<3><<<grid, kThreads, 0, s>>>(a);
       } else {
         jpeg_segment_kernel<1><<<grid, kThreads, 0, s>>>(a);
@@ -424,6 +520,7 @@ class ImageEncoderKernelGPU : public BatchedKernel {
     SCA_CHECK(quality_ >= 1 && quality_ <= 100,
               "ImageEncoder quality must be in 1..100, got " +
                   std::to_string(quality_));
+    subsampling_ = jpeg_parse_subsampling(a.get_str("subsampling", "444"));
   }
 
   void execute_batch(const BatchedElements& in, BatchedElements& out) override {
@@ -467,7 +564,7 @@ class ImageEncoderKernelGPU : public BatchedKernel {
     std::vector<u8*> bufs;
     std::vector<u64> sizes;
     jpeg_encode_gpu(frames, fi.shape[0], fi.shape[1], fi.shape[2], quality_,
-                    config_.device, stream, bufs, sizes);
+                    config_.device, stream, bufs, sizes, subsampling_);
     for (size_t i = i0; i < i1; ++i) {
       Element& e = out[i];
       e.buffer = bufs[i - i0];
@@ -479,6 +576,7 @@ class ImageEncoderKernelGPU : public BatchedKernel {
   }
 
   i32 quality_;
+  JpegSubsampling subsampling_;
 };
 
 }  // namespace

@@ -20,6 +20,7 @@
 #include "video/h264.h"
 #include "video/ingest.h"
 #include "video/mp4.h"
+#include "ops/dnn_model.h"
 #include "ops/image_decode.h"
 #include "ops/jpeg_common.h"
 #include "ops/jpeg_sync_common.h"
@@ -330,6 +331,52 @@ PYBIND11_MODULE(_core, m) {
       },
       py::arg("M"), py::arg("N"), py::arg("K"),
       py::arg("scratch_bytes") = 0, py::arg("is_conv") = false);
+
+  // The conv list of "pose1".."pose6" or "detector" as the ops build it,
+  // with each conv's place in the device blobs; pure host code, no GPU.
+  m.def("dnn_model_specs", [](const std::string& name) {
+    std::vector<dnn::ConvSpec> specs;
+    if (name == "detector") {
+      specs = detector_model_specs();
+    } else {
+      SCA_CHECK(name.size() == 5 && name.compare(0, 4, "pose") == 0 &&
+                    name[4] >= '1' && name[4] <= '6',
+                "dnn_model_specs: unknown model '" + name + "'");
+      specs = pose_model_specs(name[4] - '0');
+    }
+    py::list out;
+    for (const auto& l : dnn::model_layout(specs)) {
+      py::dict d;
+      d["name"] = l.spec.name;
+      d["in_c"] = l.spec.in_c;
+      d["out_c"] = l.spec.out_c;
+      d["r"] = l.spec.r;
+      d["s"] = l.spec.s;
+      d["stride"] = l.spec.stride;
+      d["pad"] = l.spec.pad;
+      d["relu"] = l.spec.relu;
+      d["kp"] = l.spec.kp();
+      d["np"] = l.spec.np();
+      d["w_off"] = l.w_off;
+      d["sb_off"] = l.sb_off;
+      out.append(d);
+    }
+    return out;
+  });
+
+  // The Detector op's per-frame host post-process on one frame's f32
+  // [1600][64] head maps; returns the BoundingBoxList blob. No GPU.
+  m.def(
+      "detector_postprocess",
+      [](FArr loc, FArr cls, int ih, int iw) {
+        SCA_CHECK(loc.ndim() == 2 && loc.shape(0) == 1600 &&
+                      loc.shape(1) == 64 && cls.ndim() == 2 &&
+                      cls.shape(0) == 1600 && cls.shape(1) == 64,
+                  "detector_postprocess: loc and cls must be [1600][64]");
+        SCA_CHECK(ih > 0 && iw > 0, "detector_postprocess: bad frame size");
+        return py::bytes(detector_postprocess(loc.data(), cls.data(), ih, iw));
+      },
+      py::arg("loc"), py::arg("cls"), py::arg("ih"), py::arg("iw"));
 
   // C = act((A @ B_nk^T) * scale + bias + residual). repeat > 1 launches
   // that many times on the same scratch and returns [repeat][M][N].

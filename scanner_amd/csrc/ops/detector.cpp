@@ -9,7 +9,8 @@
 //   heads: 3x3 conv -> per-anchor box deltas (A*4) and class scores (A*C),
 //          A=4 anchor sizes, C=8 classes
 // Post-process (host, per frame): sigmoid scores, decode center-form
-// deltas against the anchor grid, greedy best-NMS (util/bbox.cpp parity,
+// deltas against the anchor grid, order by score with ties in (cell,
+// anchor) order, keep the first 1000, greedy best-NMS (util/bbox.cpp parity,
 // same semantics as scanner_amd.types.nms_best), emit a BoundingBoxList
 // blob (u32 count + per box {x1,y1,x2,y2,score f32; label i32}) readable
 // by scanner_amd.types.unpack_bboxes.
@@ -24,19 +25,23 @@
 
 namespace sca {
 
-namespace {
-
 using dnn::ConvSpec;
 using dnn::DeviceModel;
 using dnn::Tensors;
+
+namespace {
 
 constexpr int kInHW = 320;
 constexpr int kFeat = 40;   // 320 / 8
 constexpr int kA = 4;       // anchors per cell
 constexpr int kC = 8;       // classes
 const float kAnchorSizes[kA] = {16.f, 32.f, 64.f, 128.f};
+constexpr float kScoreThresh = 0.5f;
+constexpr float kNmsThresh = 0.5f;
 
-std::vector<ConvSpec> detector_specs() {
+}  // namespace
+
+std::vector<ConvSpec> detector_model_specs() {
   std::vector<ConvSpec> sp;
   auto c3 = [&](const std::string& n, int ic, int oc, int stride,
                 bool relu = true) {
@@ -55,6 +60,8 @@ std::vector<ConvSpec> detector_specs() {
   return sp;
 }
 
+namespace {
+
 struct Box {
   float x1, y1, x2, y2, score;
   i32 label;
@@ -70,10 +77,8 @@ float iou(const Box& a, const Box& b) {
 }
 
 // Greedy best-first NMS (reference: bbox.cpp best_nms; same semantics as
-// scanner_amd.types.nms_best).
-std::vector<Box> nms_best(std::vector<Box> boxes, float thresh) {
-  std::sort(boxes.begin(), boxes.end(),
-            [](const Box& a, const Box& b) { return a.score > b.score; });
+// scanner_amd.types.nms_best) over boxes already in visiting order.
+std::vector<Box> nms_best(const std::vector<Box>& boxes, float thresh) {
   std::vector<Box> keep;
   std::vector<bool> alive(boxes.size(), true);
   for (size_t i = 0; i < boxes.size(); ++i) {
@@ -85,6 +90,72 @@ std::vector<Box> nms_best(std::vector<Box> boxes, float thresh) {
   }
   return keep;
 }
+
+}  // namespace
+
+// One frame's host post-process: sigmoid scores, anchor decode, clip, pre-NMS
+// top-k, NMS, blob. The candidate order is total by construction: candidates
+// are generated in (cell, anchor) order and stably sorted by score
+// descending, so equal scores (the normal case: sigmoids of bf16 logits)
+// keep (cell, anchor) order through the top-k cut and the NMS visit.
+std::string detector_postprocess(const f32* lf, const f32* cf, int ih,
+                                 int iw) {
+  float sx = (float)iw / kInHW, sy = (float)ih / kInHW;
+  std::vector<Box> cand;
+  for (int cell = 0; cell < kFeat * kFeat; ++cell) {
+    float cxg = (cell % kFeat + 0.5f) * 8.f;
+    float cyg = (cell / kFeat + 0.5f) * 8.f;
+    for (int a = 0; a < kA; ++a) {
+      // best class for this anchor
+      int best_c = 0;
+      float best_s = -1e30f;
+      for (int c = 0; c < kC; ++c) {
+        float v = cf[(size_t)cell * 64 + a * kC + c];
+        if (v > best_s) {
+          best_s = v;
+          best_c = c;
+        }
+      }
+      float score = 1.f / (1.f + std::exp(-best_s));
+      if (score < kScoreThresh) continue;
+      const f32* d = lf + (size_t)cell * 64 + a * 4;
+      float aw = kAnchorSizes[a];
+      float cx = cxg + std::tanh(d[0]) * aw;
+      float cy = cyg + std::tanh(d[1]) * aw;
+      float bw = aw * std::exp(std::min(2.f, d[2]));
+      float bh = aw * std::exp(std::min(2.f, d[3]));
+      Box b;
+      b.x1 = std::max(0.f, (cx - bw / 2) * sx);
+      b.y1 = std::max(0.f, (cy - bh / 2) * sy);
+      b.x2 = std::min((float)iw, (cx + bw / 2) * sx);
+      b.y2 = std::min((float)ih, (cy + bh / 2) * sy);
+      if (b.x2 <= b.x1 || b.y2 <= b.y1) continue;
+      b.score = score;
+      b.label = best_c;
+      cand.push_back(b);
+    }
+  }
+  std::stable_sort(cand.begin(), cand.end(), [](const Box& a, const Box& b) {
+    return a.score > b.score;
+  });
+  // standard SSD pre-NMS top-k: bounds the O(k^2) NMS on dense
+  // candidate sets (random-init heads score half the anchor grid)
+  constexpr size_t kPreNmsTopK = 1000;
+  if (cand.size() > kPreNmsTopK) cand.resize(kPreNmsTopK);
+  auto kept = nms_best(cand, kNmsThresh);
+  // BoundingBoxList blob (types.py format: '<I' count + '<5fi' boxes)
+  std::string blob(4 + kept.size() * 24, '\0');
+  u32 cnt = (u32)kept.size();
+  std::memcpy(&blob[0], &cnt, 4);
+  char* p = &blob[4];
+  for (auto& b : kept) {
+    std::memcpy(p, &b, 24);
+    p += 24;
+  }
+  return blob;
+}
+
+namespace {
 
 class DetectorKernelGPU : public BatchedKernel {
  public:
@@ -98,8 +169,6 @@ class DetectorKernelGPU : public BatchedKernel {
     auto a = mp::decode(cfg.args);
     weights_file_ = a.get_str("weights_file", "");
     seed_ = (u64)a.get_int("seed", 777);
-    score_thresh_ = 0.5f;
-    nms_thresh_ = 0.5f;
     model_ = dnn::get_model("detector", cfg.device, weights_file_, seed_,
                             [&]() {
                               Tensors ts;
@@ -116,9 +185,16 @@ class DetectorKernelGPU : public BatchedKernel {
                                 }
                               }
                               return dnn::build_device_model(
-                                  cfg.device, detector_specs(),
+                                  cfg.device, detector_model_specs(),
                                   std::move(ts), seed_);
                             });
+    // Numerics-test tap, as ResNet50 has: "pre" or a conv name. The forward
+    // stops there and the op outputs that activation per frame as f32
+    // [h][w][np], np being the GEMM-padded channel count.
+    debug_tap_ = a.get_str("debug_tap", "");
+    SCA_CHECK(debug_tap_.empty() || debug_tap_ == "pre" ||
+                  model_->by_name.count(debug_tap_),
+              "Detector: unknown debug_tap '" + debug_tap_ + "'");
   }
 
   void execute_batch(const BatchedElements& in, BatchedElements& out) override {
@@ -169,8 +245,22 @@ class DetectorKernelGPU : public BatchedKernel {
     memcpy_buffer(d_ptrs, dev, (const u8*)ptrs.data(), CPU_DEVICE,
                   n * sizeof(u8*));
 
+    // The tapped activation, once the forward has reached it.
+    const u8* tap_buf = nullptr;
+    int tap_h = 0, tap_w = 0, tap_c = 0;
+    auto tap = [&](const std::string& name, const u8* buf, int th, int tw,
+                   int tc) -> bool {
+      if (debug_tap_ != name) return false;
+      tap_buf = buf;
+      tap_h = th;
+      tap_w = tw;
+      tap_c = tc;
+      return true;
+    };
+
+    // Returns true when `name` is the tap: the forward stops there.
     auto conv = [&](const std::string& name, const u8* x, int h, int w,
-                    u8* y, int& oh, int& ow) {
+                    u8* y, int& oh, int& ow) -> bool {
       const auto& e = model_->convs[model_->by_name.at(name)];
       const ConvSpec& sp = e.spec;
       oh = (h + 2 * sp.pad - sp.r) / sp.stride + 1;
@@ -194,25 +284,52 @@ class DetectorKernelGPU : public BatchedKernel {
         g.A = colbuf;
         gemm_bf16(g, s);
       }
+      return tap(name, y, oh, ow, sp.np());
     };
 
-    f32* mean = model_->mean;
-    preprocess_frames_bf16(d_ptrs, n, ih, iw, ic, kInHW, pre, mean, mean + 3,
-                           s, /*out_c=*/8);
-    int h = kInHW, w = kInHW, oh, ow;
-    u8* x = pre;
-    u8* bufs[2] = {actA, actB};
-    int cur = 0;
-    for (const char* name : {"b1", "b2", "b3", "b4", "b5", "b6", "head"}) {
-      conv(name, x, h, w, bufs[cur], oh, ow);
-      x = bufs[cur];
-      cur ^= 1;
-      h = oh;
-      w = ow;
+    auto forward = [&]() {
+      f32* mean = model_->mean;
+      preprocess_frames_bf16(d_ptrs, n, ih, iw, ic, kInHW, pre, mean,
+                             mean + 3, s, /*out_c=*/8);
+      if (tap("pre", pre, kInHW, kInHW, 8)) return;
+      int h = kInHW, w = kInHW, oh, ow;
+      u8* x = pre;
+      u8* bufs[2] = {actA, actB};
+      int cur = 0;
+      for (const char* name : {"b1", "b2", "b3", "b4", "b5", "b6", "head"}) {
+        if (conv(name, x, h, w, bufs[cur], oh, ow)) return;
+        x = bufs[cur];
+        cur ^= 1;
+        h = oh;
+        w = ow;
+      }
+      SCA_CHECK(h == kFeat && w == kFeat, "detector feature size mismatch");
+      if (conv("loc", x, h, w, loc, oh, ow)) return;
+      if (conv("cls", x, h, w, cls, oh, ow)) return;
+    };
+    forward();
+
+    if (!debug_tap_.empty()) {
+      SCA_CHECK(tap_buf,
+                "Detector: debug_tap '" + debug_tap_ + "' not reached");
+      // This op's outputs live on the host: cast on the device, then one
+      // host buffer per frame.
+      size_t bytes = (size_t)tap_h * tap_w * tap_c * 4;
+      u8* tap_f = new_buffer(dev, (size_t)n * bytes);
+      bf16_rows_to_f32(tap_buf, n * tap_h * tap_w, tap_c, tap_c, tap_f, s);
+      sync_per_thread_stream();
+      for (int f = 0; f < n; ++f) {
+        Element e;
+        e.size = bytes;
+        e.buffer = new_buffer(CPU_DEVICE, bytes);
+        e.device = CPU_DEVICE;
+        memcpy_buffer(e.buffer, CPU_DEVICE, tap_f + (size_t)f * bytes, dev,
+                      bytes);
+        out[0].push_back(e);
+      }
+      delete_buffer(dev, tap_f);
+      return;
     }
-    SCA_CHECK(h == kFeat && w == kFeat, "detector feature size mismatch");
-    conv("loc", x, h, w, loc, oh, ow);
-    conv("cls", x, h, w, cls, oh, ow);
 
     // Small maps: bring both heads to the host as f32 and post-process.
     i64 cells = (i64)n * kFeat * kFeat;
@@ -228,68 +345,15 @@ class DetectorKernelGPU : public BatchedKernel {
                   cls_h.size() * 4);
 
     // Per frame: sigmoid scores, decode anchors, NMS, pack.
-    float sx = (float)iw / kInHW, sy = (float)ih / kInHW;
     for (int f = 0; f < n; ++f) {
-      std::vector<Box> cand;
-      const f32* lf = loc_h.data() + (size_t)f * kFeat * kFeat * 64;
-      const f32* cf = cls_h.data() + (size_t)f * kFeat * kFeat * 64;
-      for (int cell = 0; cell < kFeat * kFeat; ++cell) {
-        float cxg = (cell % kFeat + 0.5f) * 8.f;
-        float cyg = (cell / kFeat + 0.5f) * 8.f;
-        for (int a = 0; a < kA; ++a) {
-          // best class for this anchor
-          int best_c = 0;
-          float best_s = -1e30f;
-          for (int c = 0; c < kC; ++c) {
-            float v = cf[(size_t)cell * 64 + a * kC + c];
-            if (v > best_s) {
-              best_s = v;
-              best_c = c;
-            }
-          }
-          float score = 1.f / (1.f + std::exp(-best_s));
-          if (score < score_thresh_) continue;
-          const f32* d = lf + (size_t)cell * 64 + a * 4;
-          float aw = kAnchorSizes[a];
-          float cx = cxg + std::tanh(d[0]) * aw;
-          float cy = cyg + std::tanh(d[1]) * aw;
-          float bw = aw * std::exp(std::min(2.f, d[2]));
-          float bh = aw * std::exp(std::min(2.f, d[3]));
-          Box b;
-          b.x1 = std::max(0.f, (cx - bw / 2) * sx);
-          b.y1 = std::max(0.f, (cy - bh / 2) * sy);
-          b.x2 = std::min((float)iw, (cx + bw / 2) * sx);
-          b.y2 = std::min((float)ih, (cy + bh / 2) * sy);
-          if (b.x2 <= b.x1 || b.y2 <= b.y1) continue;
-          b.score = score;
-          b.label = best_c;
-          cand.push_back(b);
-        }
-      }
-      // standard SSD pre-NMS top-k: bounds the O(k^2) NMS on dense
-      // candidate sets (random-init heads score half the anchor grid)
-      constexpr size_t kPreNmsTopK = 1000;
-      if (cand.size() > kPreNmsTopK) {
-        std::partial_sort(cand.begin(), cand.begin() + kPreNmsTopK,
-                          cand.end(), [](const Box& a, const Box& b) {
-                            return a.score > b.score;
-                          });
-        cand.resize(kPreNmsTopK);
-      }
-      auto kept = nms_best(std::move(cand), nms_thresh_);
-      // BoundingBoxList blob (types.py format: '<I' count + '<5fi' boxes)
-      size_t blob = 4 + kept.size() * 24;
+      std::string blob = detector_postprocess(
+          loc_h.data() + (size_t)f * kFeat * kFeat * 64,
+          cls_h.data() + (size_t)f * kFeat * kFeat * 64, ih, iw);
       Element e;
-      e.size = blob;
-      e.buffer = new_buffer(CPU_DEVICE, blob);
+      e.size = blob.size();
+      e.buffer = new_buffer(CPU_DEVICE, blob.size());
       e.device = CPU_DEVICE;
-      u32 cnt = (u32)kept.size();
-      std::memcpy(e.buffer, &cnt, 4);
-      u8* p = e.buffer + 4;
-      for (auto& b : kept) {
-        std::memcpy(p, &b, 24);
-        p += 24;
-      }
+      std::memcpy(e.buffer, blob.data(), blob.size());
       out[0].push_back(e);
     }
   }
@@ -297,7 +361,7 @@ class DetectorKernelGPU : public BatchedKernel {
  private:
   std::string weights_file_;
   u64 seed_;
-  float score_thresh_, nms_thresh_;
+  std::string debug_tap_;
   std::shared_ptr<DeviceModel> model_;
   u8* bufs_[9] = {};
   u64 gen_ = 0;

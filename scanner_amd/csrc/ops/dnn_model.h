@@ -80,15 +80,32 @@ inline u16 f32_to_bf16_host(f32 v) {
   return (u16)(bits >> 16);
 }
 
+// Where each conv of a spec list lives in the two device blobs: weights
+// are [np][kp] bf16 per conv, scale/bias 2 * np f32 per conv, both packed
+// in spec order.
+struct ConvLayout {
+  ConvSpec spec;
+  size_t w_off;   // bf16 elements
+  size_t sb_off;  // f32 elements (scale at sb_off, bias at sb_off+np)
+};
+
+inline std::vector<ConvLayout> model_layout(
+    const std::vector<ConvSpec>& specs) {
+  std::vector<ConvLayout> out;
+  size_t w_elems = 0, sb_elems = 0;
+  for (const auto& sp : specs) {
+    out.push_back({sp, w_elems, sb_elems});
+    w_elems += (size_t)sp.np() * sp.kp();
+    sb_elems += 2 * (size_t)sp.np();
+  }
+  return out;
+}
+
 struct DeviceModel {
   DeviceHandle dev;
   u8* weights = nullptr;    // bf16
   u8* scalebias = nullptr;  // f32: per conv scale then bias (padded np)
-  struct Entry {
-    ConvSpec spec;
-    size_t w_off;   // bf16 elements
-    size_t sb_off;  // f32 elements (scale at sb_off, bias at sb_off+np)
-  };
+  using Entry = ConvLayout;
   std::vector<Entry> convs;
   std::map<std::string, int> by_name;
   float* mean = nullptr;  // 3 floats mean + 3 std (imagenet normalization)
@@ -117,11 +134,11 @@ inline std::shared_ptr<DeviceModel> build_device_model(
   model->dev = dev;
   model->generation = memory_generation();
   size_t w_elems = 0, sb_elems = 0;
-  for (const auto& sp : specs) {
-    model->by_name[sp.name] = (int)model->convs.size();
-    model->convs.push_back({sp, w_elems, sb_elems});
-    w_elems += (size_t)sp.np() * sp.kp();
-    sb_elems += 2 * (size_t)sp.np();
+  for (const auto& l : model_layout(specs)) {
+    model->by_name[l.spec.name] = (int)model->convs.size();
+    model->convs.push_back(l);
+    w_elems = l.w_off + (size_t)l.spec.np() * l.spec.kp();
+    sb_elems = l.sb_off + 2 * (size_t)l.spec.np();
   }
   std::vector<u16> wh(w_elems, 0);
   std::vector<f32> sbh(sb_elems, 0.f);
@@ -188,4 +205,14 @@ inline std::shared_ptr<DeviceModel> get_model(
 }
 
 }  // namespace dnn
+
+// The spec lists of the two multi-conv ops (pose.cpp, detector.cpp), and the
+// detector's per-frame host post-process, exposed for the tests.
+std::vector<dnn::ConvSpec> pose_model_specs(int stages);
+std::vector<dnn::ConvSpec> detector_model_specs();
+// loc/cls: one frame's [1600][64] f32 head maps. Returns the
+// BoundingBoxList blob.
+std::string detector_postprocess(const f32* loc, const f32* cls, int ih,
+                                 int iw);
+
 }  // namespace sca

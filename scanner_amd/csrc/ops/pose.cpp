@@ -26,18 +26,20 @@
 
 namespace sca {
 
-namespace {
-
 using dnn::ConvSpec;
 using dnn::DeviceModel;
 using dnn::Tensors;
+
+namespace {
 
 constexpr int kInHW = 368;
 constexpr int kFeatHW = 46;  // 368 / 8
 constexpr int kPafC = 38;    // L branch (part affinity fields)
 constexpr int kHeatC = 19;   // S branch (keypoint heatmaps)
 
-std::vector<ConvSpec> pose_specs(int stages) {
+}  // namespace
+
+std::vector<ConvSpec> pose_model_specs(int stages) {
   std::vector<ConvSpec> sp;
   auto c3 = [&](const std::string& n, int ic, int oc, int stride) {
     sp.push_back({n, ic, oc, 3, 3, stride, 1, true});
@@ -71,6 +73,8 @@ std::vector<ConvSpec> pose_specs(int stages) {
   return sp;
 }
 
+namespace {
+
 class PoseKernelGPU : public BatchedKernel {
  public:
   explicit PoseKernelGPU(const KernelConfig& cfg) : BatchedKernel(cfg) {
@@ -95,9 +99,18 @@ class PoseKernelGPU : public BatchedKernel {
                                 }
                               }
                               return dnn::build_device_model(
-                                  cfg.device, pose_specs(stages_),
+                                  cfg.device, pose_model_specs(stages_),
                                   std::move(ts), seed_);
                             });
+    // Numerics-test tap, as ResNet50 has: "pre", a conv name or "cat<t>"
+    // (t >= 2). The forward stops there and the op outputs that activation
+    // per frame as f32 [h][w][np], np being the GEMM-padded channel count.
+    debug_tap_ = a.get_str("debug_tap", "");
+    bool known = debug_tap_.empty() || debug_tap_ == "pre" ||
+                 model_->by_name.count(debug_tap_);
+    for (int t = 2; t <= stages_ && !known; ++t)
+      known = debug_tap_ == "cat" + std::to_string(t);
+    SCA_CHECK(known, "Pose: unknown debug_tap '" + debug_tap_ + "'");
   }
 
   ~PoseKernelGPU() override {
@@ -115,6 +128,15 @@ class PoseKernelGPU : public BatchedKernel {
     SCA_CHECK(f0.is_frame && f0.device.is_gpu(), "Pose needs GPU frames");
     int ih = f0.frame_info.shape[0], iw = f0.frame_info.shape[1],
         ic = f0.frame_info.shape[2];
+    // Geometry is taken from frame 0 for the whole batch, so preprocess
+    // would read past the end of a smaller frame: every element must match.
+    for (int k = 1; k < n; ++k) {
+      const Element& fk = in[0][k];
+      SCA_CHECK(fk.is_frame && fk.frame_info.shape[0] == ih &&
+                    fk.frame_info.shape[1] == iw &&
+                    fk.frame_info.shape[2] == ic,
+                "Pose batch has mixed frame geometries");
+    }
 
     // Persistent workspace sized for max_batch (no per-execute pool
     // traffic). Peak activation: b1 output n x 368^2 x 64; peak im2col:
@@ -154,8 +176,22 @@ class PoseKernelGPU : public BatchedKernel {
     memcpy_buffer(d_ptrs, dev, (const u8*)ptrs.data(), CPU_DEVICE,
                   n * sizeof(u8*));
 
+    // The tapped activation, once the forward has reached it.
+    const u8* tap_buf = nullptr;
+    int tap_h = 0, tap_w = 0, tap_c = 0;
+    auto tap = [&](const std::string& name, const u8* buf, int th, int tw,
+                   int tc) -> bool {
+      if (debug_tap_ != name) return false;
+      tap_buf = buf;
+      tap_h = th;
+      tap_w = tw;
+      tap_c = tc;
+      return true;
+    };
+
+    // Returns true when `name` is the tap: the forward stops there.
     auto conv = [&](const std::string& name, const u8* x, int h, int w,
-                    u8* y, int& oh, int& ow) {
+                    u8* y, int& oh, int& ow) -> bool {
       const auto& e = model_->convs[model_->by_name.at(name)];
       const ConvSpec& sp = e.spec;
       oh = (h + 2 * sp.pad - sp.r) / sp.stride + 1;
@@ -186,47 +222,71 @@ class PoseKernelGPU : public BatchedKernel {
       } else {
         gemm_bf16(g, s);
       }
+      return tap(name, y, oh, ow, sp.np());
     };
 
-    // ---- backbone ----
-    f32* mean = model_->mean;
-    preprocess_frames_bf16(d_ptrs, n, ih, iw, ic, kInHW, pre, mean, mean + 3,
-                           s, /*out_c=*/8);
-    int h = kInHW, w = kInHW, oh, ow;
-    const char* bb[] = {"b1", "b2", "b3", "b4", "b5", "b6", "b7"};
-    u8* x = pre;
-    u8* bufs[2] = {actA, actB};
-    int cur = 0;
-    for (const char* name : bb) {
-      conv(name, x, h, w, bufs[cur], oh, ow);
-      x = bufs[cur];
-      cur ^= 1;
-      h = oh;
-      w = ow;
-    }
-    conv("b8", x, h, w, feat, oh, ow);  // F: n x 46 x 46 x 128
-    SCA_CHECK(oh == kFeatHW && ow == kFeatHW, "pose feature size mismatch");
+    auto forward = [&]() {
+      // ---- backbone ----
+      f32* mean = model_->mean;
+      preprocess_frames_bf16(d_ptrs, n, ih, iw, ic, kInHW, pre, mean, mean + 3,
+                             s, /*out_c=*/8);
+      if (tap("pre", pre, kInHW, kInHW, 8)) return;
+      int h = kInHW, w = kInHW, oh, ow;
+      const char* bb[] = {"b1", "b2", "b3", "b4", "b5", "b6", "b7"};
+      u8* x = pre;
+      u8* bufs[2] = {actA, actB};
+      int cur = 0;
+      for (const char* name : bb) {
+        if (conv(name, x, h, w, bufs[cur], oh, ow)) return;
+        x = bufs[cur];
+        cur ^= 1;
+        h = oh;
+        w = ow;
+      }
+      // F: n x 46 x 46 x 128
+      if (conv("b8", x, h, w, feat, oh, ow)) return;
+      SCA_CHECK(oh == kFeatHW && ow == kFeatHW, "pose feature size mismatch");
 
-    // ---- stages ----
-    for (int t = 1; t <= stages_; ++t) {
-      const u8* stage_in;
-      int sh = kFeatHW, sw = kFeatHW;
-      if (t == 1) {
-        stage_in = feat;
-      } else {
-        concat3_bf16(feat, 128, 128, brL, kPafC, 64, brS, kHeatC, 64,
-                     (i64)featpix, cat, 192, s);
-        stage_in = cat;
+      // ---- stages ----
+      for (int t = 1; t <= stages_; ++t) {
+        const u8* stage_in;
+        int sh = kFeatHW, sw = kFeatHW;
+        if (t == 1) {
+          stage_in = feat;
+        } else {
+          concat3_bf16(feat, 128, 128, brL, kPafC, 64, brS, kHeatC, 64,
+                       (i64)featpix, cat, 192, s);
+          stage_in = cat;
+          if (tap("cat" + std::to_string(t), cat, sh, sw, 192)) return;
+        }
+        for (const char* br : {"L", "S"}) {
+          std::string p = "s" + std::to_string(t) + br;
+          u8* outbuf = br[0] == 'L' ? brL : brS;
+          if (conv(p + "_1", stage_in, sh, sw, brT, oh, ow)) return;
+          if (conv(p + "_2", brT, sh, sw, brU, oh, ow)) return;
+          if (conv(p + "_3", brU, sh, sw, brT, oh, ow)) return;
+          if (conv(p + "_4", brT, sh, sw, brU, oh, ow)) return;
+          if (conv(p + "_5", brU, sh, sw, outbuf, oh, ow)) return;
+        }
       }
-      for (const char* br : {"L", "S"}) {
-        std::string p = "s" + std::to_string(t) + br;
-        u8* outbuf = br[0] == 'L' ? brL : brS;
-        conv(p + "_1", stage_in, sh, sw, brT, oh, ow);
-        conv(p + "_2", brT, sh, sw, brU, oh, ow);
-        conv(p + "_3", brU, sh, sw, brT, oh, ow);
-        conv(p + "_4", brT, sh, sw, brU, oh, ow);
-        conv(p + "_5", brU, sh, sw, outbuf, oh, ow);
+    };
+    forward();
+
+    if (!debug_tap_.empty()) {
+      SCA_CHECK(tap_buf, "Pose: debug_tap '" + debug_tap_ + "' not reached");
+      size_t elems = (size_t)tap_h * tap_w * tap_c;
+      u8* out_block = new_block_buffer(dev, (size_t)n * elems * 4, n);
+      bf16_rows_to_f32(tap_buf, n * tap_h * tap_w, tap_c, tap_c,
+                       out_block, s);
+      sync_per_thread_stream();
+      for (int i = 0; i < n; ++i) {
+        Element e;
+        e.buffer = out_block + (size_t)i * elems * 4;
+        e.size = elems * 4;
+        e.device = dev;
+        out[0].push_back(e);
       }
+      return;
     }
 
     // ---- keypoints: argmax over the final heatmaps ----
@@ -249,6 +309,7 @@ class PoseKernelGPU : public BatchedKernel {
   std::string weights_file_;
   u64 seed_;
   int stages_;
+  std::string debug_tap_;
   std::shared_ptr<DeviceModel> model_;
   u8* bufs_[11] = {};
   u64 gen_ = 0;

@@ -337,6 +337,16 @@ void ResNet50KernelGPU::execute_batch(const BatchedElements& in,
   const Element& f0 = in[0][0];
   SCA_CHECK(f0.is_frame && f0.device.is_gpu(),
             "ResNet50 needs GPU frame input");
+  // Geometry is taken from frame 0 for the whole batch, so preprocess would
+  // read past the end of a smaller frame: every element must match.
+  for (int k = 1; k < n; ++k) {
+    const Element& fk = in[0][k];
+    SCA_CHECK(fk.is_frame &&
+                  fk.frame_info.shape[0] == f0.frame_info.shape[0] &&
+                  fk.frame_info.shape[1] == f0.frame_info.shape[1] &&
+                  fk.frame_info.shape[2] == f0.frame_info.shape[2],
+              "ResNet50 batch has mixed frame geometries");
+  }
   ensure_workspace(f0.frame_info.shape[0], f0.frame_info.shape[1],
                    f0.frame_info.shape[2]);
 

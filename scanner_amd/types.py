@@ -90,12 +90,13 @@ def _iou_matrix(a, b):
 
 def nms_best(boxes, iou_threshold=0.5):
     """Greedy best-first NMS (parity: bbox.cpp best_nms): keep the highest-
-    scoring box, drop overlaps, repeat."""
+    scoring box, drop overlaps, repeat. Boxes of equal score are visited in
+    the order given (the Detector op's order: stable sort by score)."""
     if not boxes:
         return []
     arr = np.array([[b.x1, b.y1, b.x2, b.y2] for b in boxes], np.float32)
     scores = np.array([b.score for b in boxes], np.float32)
-    order = np.argsort(-scores)
+    order = np.argsort(-scores, kind="stable")
     keep = []
     alive = np.ones(len(boxes), bool)
     for i in order:

@@ -336,6 +336,28 @@ def assert_mutations_flagged(A, B, inp, K, what):
     return rates
 
 
+# ---- preprocess (resize + normalise) ----
+
+PRE_MEAN = np.array([0.485, 0.456, 0.406], np.float32)
+PRE_STD = np.array([0.229, 0.224, 0.225], np.float32)
+
+
+def preprocess_ref(frames, ohw, mean=PRE_MEAN, std=PRE_STD):
+    """float64 bilinear resize (half-pixel centres) of u8 [n][h][w][3]
+    frames to ohw x ohw, then (y / 255 - mean) / std."""
+    import torch
+    import torch.nn.functional as F
+    t = torch.from_numpy(frames.astype(np.float64)).permute(0, 3, 1, 2)
+    y = F.interpolate(t, size=(ohw, ohw), mode="bilinear",
+                      align_corners=False).permute(0, 2, 3, 1).numpy()
+    return (y / 255.0 - mean.astype(np.float64)) / std.astype(np.float64)
+
+
+def preprocess_tolerance(ref, ih, iw, std=PRE_STD):
+    return (U_BF16 * np.abs(ref) +
+            (2.0 ** -22 * max(ih, iw) + 2.0 ** -20) / float(std.min()))
+
+
 # ---- convolution ----
 
 def im2col_ref(x, r, s, stride, pad, kp):

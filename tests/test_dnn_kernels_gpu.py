@@ -316,21 +316,14 @@ def test_heatmap_argmax(tie):
 
 @pytest.mark.parametrize("geom", [(37, 53, 32, 8), (20, 24, 48, 3)], ids=str)
 def test_preprocess(geom):
-    import torch
-    import torch.nn.functional as F
     ih, iw, ohw, oc = geom
     rng = np.random.RandomState(ih)
     frames = rng.randint(0, 256, (2, ih, iw, 3)).astype(np.uint8)
-    mean = np.array([0.485, 0.456, 0.406], np.float32)
-    std = np.array([0.229, 0.224, 0.225], np.float32)
+    mean, std = R.PRE_MEAN, R.PRE_STD
     got = _core.preprocess_frames_bf16_test(frames, ohw, oc, mean, std)
     assert got.shape == (2, ohw, ohw, oc)
-    t = torch.from_numpy(frames.astype(np.float64)).permute(0, 3, 1, 2)
-    y = F.interpolate(t, size=(ohw, ohw), mode="bilinear",
-                      align_corners=False).permute(0, 2, 3, 1).numpy()
-    ref = (y / 255.0 - mean.astype(np.float64)) / std.astype(np.float64)
-    tol = (R.U_BF16 * np.abs(ref) +
-           (2.0 ** -22 * max(ih, iw) + 2.0 ** -20) / float(std.min()))
+    ref = R.preprocess_ref(frames, ohw, mean, std)
+    tol = R.preprocess_tolerance(ref, ih, iw, std)
     worst = R.assert_within(got[..., :3], ref, tol, f"preprocess {geom}")
     print(f"worst err/tol preprocess {geom}: {worst:.3f}")
     assert not got[..., 3:].any()  # pad channels exactly zero

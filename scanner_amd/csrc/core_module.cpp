@@ -1534,6 +1534,93 @@ PYBIND11_MODULE(_core, m) {
       py::arg("frames"), py::arg("stencil") = std::vector<i32>{0},
       py::arg("packed") = true, py::arg("then_op") = "",
       py::arg("then_args") = py::bytes());
+  // Seconds for `iters` execute() calls of ONE Resize kernel object on
+  // `batch` resident sh x sw x c noise frames (tools/bench_resize.py): the
+  // steady state of a pipeline instance, tables and workspace cached. On
+  // the GPU the clock stops after the stream has drained.
+  m.def(
+      "resize_bench",
+      [](i32 device_type, const py::bytes& args_b, i32 sh, i32 sw, i32 c,
+         i32 batch, i32 iters) {
+        SCA_CHECK(device_type == 0 || device_type == 1,
+                  "resize_bench: bad device type");
+        const bool gpu = device_type == (i32)DeviceType::GPU;
+        SCA_CHECK(!gpu || have_gpu(), "resize_bench needs a GPU");
+        SCA_CHECK(sh > 0 && sw > 0 && c > 0 && batch > 0 && iters > 0,
+                  "resize_bench: empty benchmark");
+        const DeviceHandle dev = gpu ? kTestDev : CPU_DEVICE;
+        const size_t fsize = (size_t)sh * sw * c;
+        u8* block = new_block_buffer(dev, fsize * batch, 1);
+        double secs = 0;
+        try {
+          {
+            std::vector<u8> host(fsize * batch);
+            u32 x = 2654435761u;
+            for (u8& b : host) {
+              x ^= x << 13; x ^= x >> 17; x ^= x << 5;
+              b = (u8)(x >> 24);
+            }
+            memcpy_buffer(block, dev, host.data(), CPU_DEVICE, host.size());
+          }
+          const KernelFactory& f =
+              kernel_registry().get("Resize", (DeviceType)device_type);
+          KernelConfig cfg;
+          cfg.device = dev;
+          cfg.output_device = dev;
+          cfg.input_columns = {"frame"};
+          cfg.output_columns = {"frame"};
+          std::string args(args_b);
+          cfg.args.assign(args.begin(), args.end());
+          cfg.max_batch = batch;
+          cfg.hip_stream = gpu ? per_thread_hip_stream() : nullptr;
+          std::unique_ptr<BaseKernel> kernel = f.make(cfg);
+          StenciledElements in(1);
+          in[0].resize(batch);
+          for (i32 i = 0; i < batch; ++i) {
+            Element e;
+            e.is_frame = true;
+            e.frame_info.shape[0] = sh;
+            e.frame_info.shape[1] = sw;
+            e.frame_info.shape[2] = c;
+            e.frame_info.type = FrameType::U8;
+            e.size = fsize;
+            e.device = dev;
+            e.index = i;
+            e.buffer = block + (size_t)i * fsize;
+            in[0][i].push_back(e);
+          }
+          py::gil_scoped_release rel;
+          auto once = [&] {
+            BatchedElements out(1);
+            try {
+              kernel->execute(in, out);
+            } catch (...) {
+              if (gpu) sync_per_thread_stream();
+              for (Element& e : out[0])
+                if (e.buffer) delete_buffer(e.device, e.buffer);
+              throw;
+            }
+            // an output goes back to the pool only once its kernel is done
+            if (gpu) sync_per_thread_stream();
+            for (Element& e : out[0])
+              if (e.buffer) delete_buffer(e.device, e.buffer);
+          };
+          once();  // tables, workspace
+          auto t0 = std::chrono::steady_clock::now();
+          for (i32 it = 0; it < iters; ++it) once();
+          secs = std::chrono::duration<double>(
+                     std::chrono::steady_clock::now() - t0)
+                     .count();
+        } catch (...) {
+          delete_buffer(dev, block);
+          throw;
+        }
+        delete_buffer(dev, block);
+        return secs;
+      },
+      py::arg("device_type"), py::arg("args_bytes"), py::arg("sh"),
+      py::arg("sw"), py::arg("c") = 3, py::arg("batch") = 16,
+      py::arg("iters") = 1);
   m.def("register_python_op", &register_python_op_binding);
 
   py::class_<Database, std::shared_ptr<Database>>(m, "Database")

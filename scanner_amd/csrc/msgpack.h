@@ -64,6 +64,14 @@ struct Value {
     auto it = m.find(k);
     return it == m.end() || it->second.is_nil() ? dflt : it->second.as_str();
   }
+  // Python's True/False arrive as msgpack bools; 0/1 are taken as well.
+  bool get_bool(const std::string& k, bool dflt) const {
+    auto& m = as_map();
+    auto it = m.find(k);
+    if (it == m.end() || it->second.is_nil()) return dflt;
+    if (std::holds_alternative<bool>(it->second.v)) return it->second.as_bool();
+    return it->second.as_int() != 0;
+  }
   bool has(const std::string& k) const {
     auto& m = as_map();
     auto it = m.find(k);

@@ -5,8 +5,10 @@
 // here they are first-party, with GPU (HIP) counterparts in
 // kernels/image_ops.hip registered by ops/stdlib_gpu.cpp.
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstring>
+#include <map>
 #include <thread>
 #include <vector>
 
@@ -14,6 +16,7 @@
 #include "../msgpack.h"
 #include "kernel.h"
 #include "optflow_common.h"
+#include "resample_common.h"
 
 namespace sca {
 
@@ -63,7 +66,10 @@ class HistogramKernelCPU : public BatchedKernel {
   }
 };
 
-// ---- Resize: bilinear HWC u8 ----
+// ---- Resize: HWC u8. filter="bilinear" (default) is the two-tap sampler
+// below; "nearest", "box", "triangle", "cubic", "lanczos3" run the integer
+// resampler of resample_common.h. preserve_aspect fits each frame into the
+// width x height box (resample_fit), so rows may differ in shape. ----
 class ResizeKernelCPU : public BatchedKernel {
  public:
   explicit ResizeKernelCPU(const KernelConfig& cfg) : BatchedKernel(cfg) {
@@ -71,23 +77,46 @@ class ResizeKernelCPU : public BatchedKernel {
     out_w_ = (i32)a.get_int("width", 0);
     out_h_ = (i32)a.get_int("height", 0);
     SCA_CHECK(out_w_ > 0 && out_h_ > 0, "Resize needs width/height args");
+    filter_name_ = a.get_str("filter", "bilinear");
+    filter_ = resample_parse_filter(filter_name_);
+    preserve_aspect_ = a.get_bool("preserve_aspect", false);
   }
   void execute_batch(const BatchedElements& in, BatchedElements& out) override {
     for (const Element& f : in[0]) {
       SCA_CHECK(f.is_frame, "Resize needs a frame input");
       i32 h = f.frame_info.shape[0], w = f.frame_info.shape[1],
           c = f.frame_info.shape[2];
-      Element e = alloc_frame(config_.device, out_h_, out_w_, c, FrameType::U8);
+      i32 dh = out_h_, dw = out_w_;
+      if (preserve_aspect_) {
+        SCA_CHECK(h > 0 && w > 0,
+                  "Resize preserve_aspect needs a non-empty frame");
+        resample_fit(h, w, out_h_, out_w_, &dh, &dw);
+      }
+      if (filter_ != ResampleFilter::kBilinear) {
+        SCA_CHECK(f.frame_info.type == FrameType::U8,
+                  "Resize filter '" + filter_name_ + "' needs u8 frames");
+        SCA_CHECK(h > 0 && w > 0 && c > 0, "Resize needs a non-empty frame");
+        Element e = alloc_frame(config_.device, dh, dw, c, FrameType::U8);
+        out[0].push_back(e);
+        if (filter_ == ResampleFilter::kNearest) {
+          resample_nearest_cpu(f.buffer, h, w, c, e.buffer, dh, dw);
+        } else {
+          const Tables& t = tables(h, w, dh, dw);
+          resample_cpu(f.buffer, h, w, c, t.x, t.y, e.buffer, tmp_);
+        }
+        continue;
+      }
+      Element e = alloc_frame(config_.device, dh, dw, c, FrameType::U8);
       u8* dst = e.buffer;
       const u8* src = f.buffer;
-      for (i32 y = 0; y < out_h_; ++y) {
-        f32 sy = (y + 0.5f) * h / out_h_ - 0.5f;
+      for (i32 y = 0; y < dh; ++y) {
+        f32 sy = (y + 0.5f) * h / dh - 0.5f;
         i32 y0 = std::max(0, (i32)std::floor(sy));
         i32 y1 = std::min(h - 1, y0 + 1);
         f32 fy = sy - y0;
         if (fy < 0) fy = 0;
-        for (i32 x = 0; x < out_w_; ++x) {
-          f32 sx = (x + 0.5f) * w / out_w_ - 0.5f;
+        for (i32 x = 0; x < dw; ++x) {
+          f32 sx = (x + 0.5f) * w / dw - 0.5f;
           i32 x0 = std::max(0, (i32)std::floor(sx));
           i32 x1 = std::min(w - 1, x0 + 1);
           f32 fx = sx - x0;
@@ -99,7 +128,7 @@ class ResizeKernelCPU : public BatchedKernel {
             f32 v11 = src[((i64)y1 * w + x1) * c + ch];
             f32 v = v00 * (1 - fy) * (1 - fx) + v01 * (1 - fy) * fx +
                     v10 * fy * (1 - fx) + v11 * fy * fx;
-            dst[((i64)y * out_w_ + x) * c + ch] = (u8)(v + 0.5f);
+            dst[((i64)y * dw + x) * c + ch] = (u8)(v + 0.5f);
           }
         }
       }
@@ -108,7 +137,28 @@ class ResizeKernelCPU : public BatchedKernel {
   }
 
  private:
+  struct Tables {
+    ResampleAxis x, y;
+  };
+  // Tables per (sh, sw, dh, dw); the filter is fixed per kernel. A column of
+  // ever-changing sizes must not grow the cache without bound.
+  const Tables& tables(i32 sh, i32 sw, i32 dh, i32 dw) {
+    std::array<i32, 4> key{sh, sw, dh, dw};
+    auto it = tables_.find(key);
+    if (it != tables_.end()) return it->second;
+    if (tables_.size() >= 64) tables_.clear();
+    Tables t;
+    t.x = resample_build_axis(filter_, sw, dw);
+    t.y = resample_build_axis(filter_, sh, dh);
+    return tables_.emplace(key, std::move(t)).first->second;
+  }
+
   i32 out_w_, out_h_;
+  std::string filter_name_;
+  ResampleFilter filter_;
+  bool preserve_aspect_;
+  std::map<std::array<i32, 4>, Tables> tables_;
+  std::vector<i16> tmp_;
 };
 
 // ---- Blur: separable box blur (test-op parity with reference Blur) ----

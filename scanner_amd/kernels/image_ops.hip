@@ -14,6 +14,7 @@
 #include "../csrc/memory.h"
 #include "../csrc/msgpack.h"
 #include "../csrc/ops/kernel.h"
+#include "resample.h"
 
 namespace sca {
 
@@ -269,33 +270,66 @@ class ResizeKernelGPU : public BatchedKernel {
     out_w_ = (i32)a.get_int("width", 0);
     out_h_ = (i32)a.get_int("height", 0);
     SCA_CHECK(out_w_ > 0 && out_h_ > 0, "Resize needs width/height args");
+    filter_ = resample_parse_filter(a.get_str("filter", "bilinear"));
+    preserve_aspect_ = a.get_bool("preserve_aspect", false);
+    if (filter_ != ResampleFilter::kBilinear)
+      resample_ = std::make_unique<ResampleGPU>(config_.device, filter_);
   }
   void execute_batch(const BatchedElements& in, BatchedElements& out) override {
     hipStream_t s = cur_stream();
+    // the other filters: kernels/resample.hip, one launch per pass and group
+    // of same-geometry frames
+    if (resample_) {
+      std::vector<std::pair<i32, i32>> dst_hw;
+      for (const Element& f : in[0]) {
+        SCA_CHECK(f.is_frame && f.device.is_gpu(),
+                  "GPU Resize needs GPU input");
+        dst_hw.push_back(fit(f));
+      }
+      resample_->run(in[0], dst_hw, out[0], s);
+      return;
+    }
     for (const Element& f : in[0]) {
       SCA_CHECK(f.is_frame && f.device.is_gpu(), "GPU Resize needs GPU input");
       i32 h = f.frame_info.shape[0], w = f.frame_info.shape[1],
           c = f.frame_info.shape[2];
+      auto [dh, dw] = fit(f);
       Element e;
       e.is_frame = true;
-      e.frame_info.shape[0] = out_h_;
-      e.frame_info.shape[1] = out_w_;
+      e.frame_info.shape[0] = dh;
+      e.frame_info.shape[1] = dw;
       e.frame_info.shape[2] = c;
       e.frame_info.type = FrameType::U8;
       e.size = e.frame_info.size();
       e.buffer = new_buffer(config_.device, e.size);
       e.device = config_.device;
-      u64 total = (u64)out_h_ * out_w_ * c;
+      u64 total = (u64)dh * dw * c;
       int blocks = (int)std::min<u64>(2048, (total + 255) / 256);
       resize_bilinear_kernel<<<blocks, 256, 0, s>>>(f.buffer, h, w, e.buffer,
-                                                    out_h_, out_w_, c);
+                                                    dh, dw, c);
       HIPK_CHECK(hipGetLastError());
       out[0].push_back(e);
     }
   }
 
  private:
+  // (dh, dw) of a frame's output: the box itself, or the frame's own aspect
+  // fitted into it
+  std::pair<i32, i32> fit(const Element& f) const {
+    i32 dh = out_h_, dw = out_w_;
+    if (preserve_aspect_) {
+      SCA_CHECK(f.frame_info.shape[0] > 0 && f.frame_info.shape[1] > 0,
+                "Resize preserve_aspect needs a non-empty frame");
+      resample_fit(f.frame_info.shape[0], f.frame_info.shape[1], out_h_,
+                   out_w_, &dh, &dw);
+    }
+    return {dh, dw};
+  }
+
   i32 out_w_, out_h_;
+  ResampleFilter filter_;
+  bool preserve_aspect_;
+  std::unique_ptr<ResampleGPU> resample_;
 };
 
 }  // namespace

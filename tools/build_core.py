@@ -44,6 +44,7 @@ CPP_SOURCES = [
 ]
 HIP_SOURCES = [
     "kernels/image_ops.hip",
+    "kernels/resample.hip",
     "kernels/svc_codec.hip",
     "kernels/svc_encode.hip",
     "kernels/jpeg_encode.hip",

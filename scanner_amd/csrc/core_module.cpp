@@ -332,12 +332,15 @@ PYBIND11_MODULE(_core, m) {
       py::arg("M"), py::arg("N"), py::arg("K"),
       py::arg("scratch_bytes") = 0, py::arg("is_conv") = false);
 
-  // The conv list of "pose1".."pose6" or "detector" as the ops build it,
+  // The conv list of "resnet50", "pose1".."pose6" or "detector" as the ops
+  // build it,
   // with each conv's place in the device blobs; pure host code, no GPU.
   m.def("dnn_model_specs", [](const std::string& name) {
     std::vector<dnn::ConvSpec> specs;
     if (name == "detector") {
       specs = detector_model_specs();
+    } else if (name == "resnet50") {
+      specs = resnet50_model_specs();
     } else {
       SCA_CHECK(name.size() == 5 && name.compare(0, 4, "pose") == 0 &&
                     name[4] >= '1' && name[4] <= '6',

@@ -206,10 +206,12 @@ inline std::shared_ptr<DeviceModel> get_model(
 
 }  // namespace dnn
 
-// The spec lists of the two multi-conv ops (pose.cpp, detector.cpp), and the
+// The spec lists of the multi-conv ops (resnet50.cpp, pose.cpp,
+// detector.cpp), and the
 // detector's per-frame host post-process, exposed for the tests.
 std::vector<dnn::ConvSpec> pose_model_specs(int stages);
 std::vector<dnn::ConvSpec> detector_model_specs();
+std::vector<dnn::ConvSpec> resnet50_model_specs();
 // loc/cls: one frame's [1600][64] f32 head maps. Returns the
 // BoundingBoxList blob.
 std::string detector_postprocess(const f32* loc, const f32* cls, int ih,

@@ -1,7 +1,9 @@
 """ResNet-50 model family support: weight generation, tensor-file export
 for the C++ engine, and a PyTorch fp32 reference forward used by the
 numerics tests (tests/test_resnet_gpu.py compares the engine's bf16 MFMA
-path against this at fp32).
+path against this at fp32). layer_specs() and generate_layer_weights() are
+the dict-form spec list and the complete weight file of the layer-by-layer
+tests (tests/test_resnet_layers_*.py).
 
 Layer naming and the [out][r][s][in] (OHWI) weight layout mirror
 csrc/ops/resnet50.cpp exactly; BN is pre-folded into per-channel
@@ -54,6 +56,45 @@ def generate_weights(seed=0):
             ts[name + ".scale"] = rng.uniform(
                 0.7, 1.3, out_c).astype(np.float32)
         ts[name + ".bias"] = rng.normal(0, 0.05, out_c).astype(np.float32)
+    return ts
+
+
+IN_HW = 224
+
+
+def layer_specs():
+    """The convs as dicts in the engine's order, the form of
+    pose.conv_specs(): in_c is what the engine's conv consumes, so conv1
+    reads the 8 channels preprocess writes (RGB and 5 zero lanes)."""
+    specs = []
+    for (name, in_c, out_c, k, stride, pad, relu) in conv_specs():
+        specs.append(dict(name=name, in_c=8 if name == "conv1" else in_c,
+                          out_c=out_c, r=k, s=k, stride=stride, pad=pad,
+                          relu=relu))
+    return specs
+
+
+def generate_layer_weights(seed=0, conv1_channels=8):
+    """He-normal OHWI weights, scale ~ U(0.7, 1.3) (fc included), bias ~
+    N(0, 0.05) for every conv of layer_specs(). conv1.weight is 64 x 7 x 7 x
+    8 with non-zero weights in channels 3..7, which meet the zero lanes of
+    the preprocess output, so those lanes are load-bearing;
+    conv1_channels=3 gives its first three channels as the natural 64 x 7 x
+    7 x 3 tensor that the engine expands on load."""
+    assert conv1_channels in (3, 8)
+    rng = np.random.RandomState(seed)
+    ts = {}
+    for sp in layer_specs():
+        fan_in = sp["in_c"] * sp["r"] * sp["s"]
+        w = rng.normal(0, np.sqrt(2.0 / fan_in),
+                       size=(sp["out_c"], sp["r"], sp["s"], sp["in_c"]))
+        if sp["name"] == "conv1" and conv1_channels == 3:
+            w = w[..., :3]
+        ts[sp["name"] + ".weight"] = np.ascontiguousarray(w, np.float32)
+        ts[sp["name"] + ".scale"] = rng.uniform(
+            0.7, 1.3, sp["out_c"]).astype(np.float32)
+        ts[sp["name"] + ".bias"] = rng.normal(
+            0, 0.05, sp["out_c"]).astype(np.float32)
     return ts
 
 

@@ -1,11 +1,15 @@
-"""Per-layer float64 references for the Pose and Detector networks
-(test_dnn_models_cpu.py, test_dnn_models_gpu.py, test_detector_post_cpu.py).
+"""Per-layer float64 references for the Pose, Detector and ResNet-50
+networks (test_dnn_models_cpu.py, test_dnn_models_gpu.py,
+test_detector_post_cpu.py, test_resnet_layers_cpu.py,
+test_resnet_layers_gpu.py).
 
 Written from the topology comments at the top of csrc/ops/pose.cpp and
-csrc/ops/detector.cpp, not from the ops' loops: a layer is
+csrc/ops/detector.cpp and from resnet50_specs() with the bottleneck
+topology stated at resnet_nodes() below, not from the ops' loops: a layer is
 torch.nn.functional.conv2d in float64 on the bf16-exact previous activation
 and the bf16-rounded weights, then the f32 scale and bias as float64, then
-relu where the spec says so. Each layer is checked against the reference
+the bf16-exact residual where the node names one, then relu where the spec
+says so. Each layer is checked against the reference
 fed the *engine's own* previous activation (teacher forcing), so the bound
 is the single-GEMM bound of dnn_ref.tolerance with K = r * s * in_c and no
 error accumulates across layers.
@@ -31,7 +35,7 @@ def frames_45x61():
     return np.stack([smooth, noise]).astype(np.uint8)
 
 
-# ---- the two graphs: (tap name, kind, source taps), in forward order ----
+# ---- the graphs: (tap name, kind, source taps), in forward order ----
 
 def pose_nodes(stages):
     nodes = [("pre", "pre", ())]
@@ -63,6 +67,135 @@ def detector_nodes():
     return nodes
 
 
+# ResNet-50 v1.5: (blocks, mid channels, out channels, stride of the first
+# block) per stage. A bottleneck block is conv1 1x1 -> mid, conv2 3x3 -> mid
+# (the block's stride is here, not on conv1), conv3 1x1 -> out; the first
+# block of a stage projects its input with `downsample`, 1x1 at the block's
+# stride, no relu. out = relu(conv3(conv2(conv1(x))) * scale + bias + id),
+# id = downsample(x) where there is one, else x.
+RESNET_STAGES = ((3, 64, 256, 1), (4, 128, 512, 2), (6, 256, 1024, 2),
+                 (3, 512, 2048, 2))
+
+
+def resnet_nodes():
+    """pre -> conv1 7x7 s2 -> maxpool 3x3 s2 p1 -> 16 bottleneck blocks ->
+    global average -> fc. A conv3 node names two sources: its conv2 tap and
+    its identity. The downsample node comes first within its block, where
+    resnet50_specs() has it last: it is ready before conv3 needs it."""
+    nodes = [("pre", "pre", ()), ("conv1", "conv", ("pre",)),
+             ("maxpool", "maxpool", ("conv1",))]
+    prev = "maxpool"
+    b = 0
+    for count, _, _, _ in RESNET_STAGES:
+        for i in range(count):
+            p = f"block{b}"
+            identity = prev
+            if i == 0:
+                identity = p + ".downsample"
+                nodes.append((identity, "conv", (prev,)))
+            nodes += [(p + ".conv1", "conv", (prev,)),
+                      (p + ".conv2", "conv", (p + ".conv1",)),
+                      (p + ".conv3", "conv", (p + ".conv2", identity))]
+            prev = p + ".conv3"
+            b += 1
+    nodes += [("avgpool", "avgpool", (prev,)), ("fc", "conv", ("avgpool",))]
+    return nodes
+
+
+def resnet_tap_sides():
+    """{tap: h (= w)} of every node, walked from the 224 x 224 input."""
+    from scanner_amd.models import resnet50
+    specs = {s["name"]: s for s in resnet50.layer_specs()}
+    side = {}
+    for name, kind, srcs in resnet_nodes():
+        if kind == "pre":
+            side[name] = resnet50.IN_HW
+        elif kind == "avgpool":
+            side[name] = 1
+        else:
+            k, stride, pad = (3, 2, 1) if kind == "maxpool" else (
+                specs[name]["r"], specs[name]["stride"], specs[name]["pad"])
+            side[name] = (side[srcs[0]] + 2 * pad - k) // stride + 1
+    return side
+
+
+RESNET_SCRATCH = 64 << 20  # the op's split-K scratch
+
+
+def resnet_gemm_shape(spec, side, batch):
+    """(M, N, K, scratch, is_conv) as the op hands the layer to gemm_plan:
+    a 1x1 stride-1 conv (and fc) is a plain GEMM, every other conv takes
+    the implicit path."""
+    direct = spec["r"] == 1 and spec["stride"] == 1 and spec["pad"] == 0
+    return (batch * side * side, -(-spec["out_c"] // 64) * 64,
+            -(-spec["r"] * spec["s"] * spec["in_c"] // 64) * 64,
+            RESNET_SCRATCH, not direct)
+
+
+def _resnet_plans():
+    """{layer: {batch: plan}}: the dispatch paths that differ between the
+    batch the tests could afford everywhere (2) and the batch the benchmark
+    runs (64), as _core.gemm_plan gives them. Where the planner changes,
+    test_resnet_layers_cpu.py says which in-network path lost its test."""
+    p = R.plan
+    t = {}
+    for name in ("block0.downsample", "block0.conv3", "block1.conv3",
+                 "block2.conv3"):
+        # K = 64, N = 256; M = 200 704 at batch 64 walks two tiles per
+        # workgroup at the default SCANNER_SMALLK_WGS
+        t[name] = {2: p("smallk", 98, 64), 64: p("smallk", 1568, 64, tpw=2)}
+    for b in range(3, 7):       # 3x3, c = 128; block3 is stride 2
+        t[f"block{b}.conv2"] = {
+            2: p("splitk", 52, 1152, splits=4, kps=5),
+            64: p("tile128", 392, 1152, swizzle=True)}
+    for b in range(7, 13):      # 3x3, c = 256; block7 is stride 2
+        # batch 64: 6 splits wanted, 5 partials of 12 544 * 256 * 4 B fit
+        # the scratch: 8, 8, 8, 8, 4 k-steps
+        t[f"block{b}.conv2"] = {
+            2: p("splitk", 48, 2304, splits=6, kps=6),
+            64: p("splitk", 980, 2304, splits=5, kps=8)}
+    t["block13.downsample"] = {2: p("splitk", 64, 1024, splits=4, kps=4),
+                               64: p("tile128", 400, 1024, swizzle=True)}
+    t["block13.conv1"] = {2: p("splitk", 64, 1024, splits=4, kps=4),
+                          64: p("tile128", 392, 1024, swizzle=True)}
+    t["block13.conv3"] = {2: p("tile128", 16, 512, swizzle=True),
+                          64: p("tile128", 400, 512, swizzle=True)}
+    t["conv1"] = {2: p("tile64", 392, 448, swizzle=True),
+                  64: p("tile64", 12544, 448, swizzle=True)}
+    t["fc"] = {2: p("splitk", 48, 2048, splits=6, kps=6),
+               64: p("splitk", 48, 2048, splits=6, kps=6)}
+    return t
+
+
+RESNET_PLANS = _resnet_plans()
+
+
+def live_channels(node, specs):
+    """How many channels of a node's tap carry data."""
+    name, kind, srcs = node
+    if kind == "conv":
+        return specs[name]["out_c"]
+    return {"pre": 8, "cat": 192, "maxpool": 64, "avgpool": 2048}[kind]
+
+
+def noise_and_gradient_frames(n):
+    """n distinct 45 x 61 frames: the two of frames_45x61(), then seeded
+    noise (odd indices) and gradients of varying slope and offset (even)."""
+    yy, xx = np.mgrid[0:45, 0:61]
+    out = list(frames_45x61())
+    for i in range(2, n):
+        if i % 2:
+            out.append(np.random.RandomState(1000 + i).randint(
+                0, 256, (45, 61, 3)))
+        else:
+            a, b = 1 + i % 4, 1 + (i // 4) % 4
+            out.append(np.stack([(3 * i + a * xx) % 256,
+                                 (5 * i + b * yy) % 256,
+                                 (7 * i + (a * xx + b * yy) // 2) % 256],
+                                axis=-1))
+    return np.stack(out).astype(np.uint8)
+
+
 # ---- references ----
 
 def pre_ref(frames, ohw):
@@ -74,22 +207,24 @@ def pre_ref(frames, ohw):
 
 def weight_ohwi(spec, tensors):
     """The conv's bf16-rounded weights as [out][r][s][in_c]; a 3-channel b1
-    tensor is zero-extended to the 8 input channels the entry conv reads."""
+    (ResNet: conv1) tensor is zero-extended to the 8 input channels the
+    entry conv reads."""
     w = np.asarray(tensors[spec["name"] + ".weight"], np.float32)
     w = w.reshape(spec["out_c"], spec["r"], spec["s"], -1)
     if w.shape[3] != spec["in_c"]:
-        assert spec["name"] == "b1" and w.shape[3] == 3
+        assert spec["name"] in ("b1", "conv1") and w.shape[3] == 3
         w = np.concatenate(
             [w, np.zeros(w.shape[:3] + (spec["in_c"] - 3,), np.float32)], 3)
     return R.bf16_round(w)
 
 
 def layer_ref(spec, x_prev, tensors, weight=None, scale=None, bias=None,
-              relu=None):
+              relu=None, residual=None, stride=None):
     """(ref, mag) of one conv as float64 [n][oh][ow][out_c]. x_prev is the
-    bf16-exact input [n][h][w][in_c]; mag = |scale| * (|x| conv |w|) +
-    |bias|. The keyword arguments replace an operand (the seeded bugs of
-    the comparator test)."""
+    bf16-exact input [n][h][w][in_c], residual the bf16-exact
+    [n][oh][ow][out_c] operand added before the relu; mag = |scale| * (|x|
+    conv |w|) + |bias| + |residual|. The other keyword arguments replace an
+    operand (the seeded bugs of the comparator test)."""
     import torch
     import torch.nn.functional as F
     assert x_prev.shape[3] == spec["in_c"], (spec["name"], x_prev.shape)
@@ -99,16 +234,20 @@ def layer_ref(spec, x_prev, tensors, weight=None, scale=None, bias=None,
     scale = tensors[name + ".scale"] if scale is None else scale
     bias = tensors[name + ".bias"] if bias is None else bias
     relu = spec["relu"] if relu is None else relu
+    stride = spec["stride"] if stride is None else stride
+    if residual is not None:
+        assert np.array_equal(R.bf16_round(residual), residual)
     x = torch.from_numpy(x_prev.astype(np.float64)).permute(0, 3, 1, 2)
     wt = torch.from_numpy(w.astype(np.float64)).permute(0, 3, 1, 2)
 
     def run(xx, ww):
-        y = F.conv2d(xx, ww, stride=spec["stride"], padding=spec["pad"])
+        y = F.conv2d(xx, ww, stride=stride, padding=spec["pad"])
         return y.permute(0, 2, 3, 1).numpy()
 
     return R.epilogue_ref(run(x, wt), run(x.abs(), wt.abs()),
                           scale=np.asarray(scale, np.float32),
-                          bias=np.asarray(bias, np.float32), relu=relu)
+                          bias=np.asarray(bias, np.float32),
+                          residual=residual, relu=relu)
 
 
 def layer_tolerance(spec, ref, mag):
@@ -145,10 +284,21 @@ def source_of(node, taps, specs):
     return np.ascontiguousarray(taps[srcs[0]][..., :specs[name]["in_c"]])
 
 
-def emulate(nodes, spec_list, tensors, frames, ohw):
+def residual_of(node, taps, specs):
+    """The residual operand of a conv node: the first out_c channels of its
+    second source, None where it has one source."""
+    name, kind, srcs = node
+    assert kind == "conv"
+    if len(srcs) < 2:
+        return None
+    return np.ascontiguousarray(taps[srcs[1]][..., :specs[name]["out_c"]])
+
+
+def emulate(nodes, spec_list, tensors, frames, ohw, last=None):
     """The network run by the references themselves: every node's output
-    rounded to bf16 feeds the next. Returns {tap: f32 [n][h][w][c]} with
-    c = 8 for pre, out_c for a conv and 192 for a concat."""
+    rounded to bf16 feeds the next, as far as node `last`. Returns {tap: f32
+    [n][h][w][c]} with c = 8 for pre, out_c for a conv, 192 for a concat and
+    the source's for a pool."""
     specs = {s["name"]: s for s in spec_list}
     taps = {}
     for node in nodes:
@@ -159,10 +309,18 @@ def emulate(nodes, spec_list, tensors, frames, ohw):
             taps[name] = pre
         elif kind == "cat":
             taps[name] = cat_ref(*(taps[s] for s in srcs))
+        elif kind == "maxpool":
+            taps[name] = R.maxpool_ref(taps[srcs[0]]).astype(np.float32)
+        elif kind == "avgpool":
+            ref = R.avgpool_ref(taps[srcs[0]])[0]
+            taps[name] = R.bf16_round(ref).reshape(len(frames), 1, 1, -1)
         else:
             ref, _ = layer_ref(specs[name], source_of(node, taps, specs),
-                               tensors)
+                               tensors,
+                               residual=residual_of(node, taps, specs))
             taps[name] = R.bf16_round(ref)
+        if name == last:
+            break
     return taps
 
 

@@ -391,3 +391,34 @@ def conv_ref(case, inp, **ep):
         return y.permute(0, 2, 3, 1).reshape(case["M"], case["N"]).numpy()
 
     return epilogue_ref(run(x, w), run(x.abs(), w.abs()), **ep)
+
+
+# ---- pools ----
+
+def maxpool_ref(x, pad_value=None):
+    """3 x 3 stride-2 pad-1 max of an NHWC tensor as float64; the border is
+    padded with -inf, or with pad_value where one is given."""
+    import torch
+    import torch.nn.functional as F
+    t = torch.from_numpy(x.astype(np.float64)).permute(0, 3, 1, 2)
+    if pad_value is None:
+        y = F.max_pool2d(t, kernel_size=3, stride=2, padding=1)
+    else:
+        y = F.max_pool2d(F.pad(t, (1, 1, 1, 1), value=float(pad_value)),
+                         kernel_size=3, stride=2)
+    return y.permute(0, 2, 3, 1).numpy()
+
+
+def avgpool_ref(x, divisor=None):
+    """(ref, tol) of the global average of an NHWC bf16-exact tensor, as
+    [n][c] float64: hw fp32 adds and one multiply on the magnitude sum, then
+    the bf16 store."""
+    n, h, w, c = x.shape
+    hw = h * w
+    x64 = x.astype(np.float64).reshape(n, hw, c)
+    ref = x64.mean(axis=1)
+    if divisor is not None:  # a seeded bug of the comparator test
+        ref = ref * hw / divisor
+    tol = (U_BF16 * np.abs(ref) + (1 + U_BF16) * (hw + 2) * 2.0 ** -24 *
+           np.abs(x64).mean(axis=1) * hw)
+    return ref, tol

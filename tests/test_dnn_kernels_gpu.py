@@ -185,14 +185,6 @@ def test_splitk_atomic_within_tolerance(default_path_npz):
 
 # ---- helper kernels ----
 
-def _maxpool_ref(x):
-    import torch
-    import torch.nn.functional as F
-    t = torch.from_numpy(x.astype(np.float64)).permute(0, 3, 1, 2)
-    y = F.max_pool2d(t, kernel_size=3, stride=2, padding=1)
-    return y.permute(0, 2, 3, 1).numpy()
-
-
 @pytest.mark.parametrize("shape", [(2, 15, 13, 64), (1, 7, 9, 20),
                                    (1, 5, 5, 3)], ids=str)
 def test_maxpool(shape):
@@ -202,7 +194,7 @@ def test_maxpool(shape):
     for name, xx in (("mixed", x), ("all-negative", -np.abs(x) - 1.0)):
         xx = R.bf16_round(xx)
         got = _core.maxpool3x3s2_bf16_test(xx)
-        ref = _maxpool_ref(xx)
+        ref = R.maxpool_ref(xx)
         assert got.shape == ref.shape
         assert np.array_equal(got, ref.astype(np.float32)), name
     assert got.max() < 0  # the -1e30 start value never leaks out
@@ -211,11 +203,7 @@ def test_maxpool(shape):
 def test_avgpool():
     rng = np.random.RandomState(7)
     x = R.bf16_round(rng.randn(2, 7, 7, 72) + 0.5)
-    hw = 49
-    x64 = x.astype(np.float64).reshape(2, hw, 72)
-    ref = x64.mean(axis=1)
-    tol = (R.U_BF16 * np.abs(ref) + (1 + R.U_BF16) * (hw + 2) * 2.0 ** -24 *
-           np.abs(x64).mean(axis=1) * hw)
+    ref, tol = R.avgpool_ref(x)
     got = _core.global_avgpool_bf16_test(x)
     print(f"worst err/tol avgpool: "
           f"{R.assert_within(got, ref, tol, 'avgpool'):.3f}")

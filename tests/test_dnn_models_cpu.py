@@ -45,7 +45,7 @@ def test_detector_spec_parity():
 
 
 def test_unknown_model_rejected_by_name():
-    for name in ("pose0", "pose7", "pose", "resnet50", ""):
+    for name in ("pose0", "pose7", "pose", "resnet", "resnet500", ""):
         with pytest.raises(Exception, match="unknown model"):
             _core.dnn_model_specs(name)
 

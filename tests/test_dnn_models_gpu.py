@@ -14,21 +14,20 @@ generated files. A tap is fetched once per module and reused; the tap of
 one layer per model is fetched twice and must be bit-equal, which is what
 teacher forcing across calls rests on. Worst err/tol per layer is printed
 (`pytest -rP`) and tabulated in docs/testing.md; no bound is tuned from it.
+The `Net` helper and the checks live in dnn_models_net.py, shared with
+test_resnet_layers_gpu.py.
 """
-import msgpack
 import numpy as np
 import pytest
 
 import dnn_models_ref as M
-import dnn_ref as R
 import scanner_amd as sp
+from dnn_models_net import FRAMES, Net, check_conv, check_pre
 from scanner_amd import _core
 from scanner_amd.models import detector, pose
 
 pytestmark = pytest.mark.gpu
 
-GPU = 1
-FRAMES = M.frames_45x61()
 IH, IW = FRAMES.shape[1:3]
 
 # The detector head whose float64 post-process keeps a few dozen boxes with
@@ -41,85 +40,6 @@ IH, IW = FRAMES.shape[1:3]
 # to stay 0.004 away from 0.
 DET_SEED = 21
 DET_BIAS_DROP = 2.90
-
-
-class Net:
-    """One op with one weight file: its taps (each fetched once) and its
-    real output."""
-
-    def __init__(self, op, nodes, specs, tensors, path, **args):
-        self.op, self.nodes = op, nodes
-        self.specs = {s["name"]: s for s in specs}
-        self.ts = tensors
-        self.args = dict(args)
-        if tensors is not None:
-            pose.write_tensor_file(str(path), tensors)
-            self.args["weights_file"] = str(path)
-        self._taps = {}
-        self._out = None
-
-    def run(self, **extra):
-        return _core.op_kernel_test(
-            self.op, GPU, msgpack.packb(dict(self.args, **extra)),
-            list(FRAMES))
-
-    def fetch(self, name):
-        side = {"Pose": pose.IN_HW, "Detector": detector.IN_HW}[self.op]
-        rows = self.run(debug_tap=name)
-        assert len(rows) == len(FRAMES)
-        x = np.stack([np.frombuffer(r, np.float32) for r in rows])
-        node = next(n for n in self.nodes if n[0] == name)
-        c = {"pre": 8, "cat": 192}.get(node[1]) or \
-            -(-self.specs[name]["out_c"] // 64) * 64
-        assert x.shape[1] % c == 0
-        hw = int(round((x.shape[1] // c) ** 0.5))
-        assert hw * hw * c == x.shape[1] and side % hw == 0, (name, x.shape)
-        return x.reshape(len(FRAMES), hw, hw, c)
-
-    def tap(self, name):
-        if name not in self._taps:
-            self._taps[name] = self.fetch(name)
-        return self._taps[name]
-
-    def output(self):
-        if self._out is None:
-            self._out = self.run()
-        return self._out
-
-    def node(self, name):
-        return next(n for n in self.nodes if n[0] == name)
-
-    def conv_names(self):
-        return [n[0] for n in self.nodes if n[1] == "conv"]
-
-
-def check_pre(net, ohw):
-    got = net.tap("pre")
-    assert got.shape == (2, ohw, ohw, 8)
-    ref, tol = M.pre_ref(FRAMES, ohw)
-    worst = R.assert_within(got[..., :3], ref, tol, f"{net.op} pre")
-    assert not got[..., 3:].view(np.uint32).any(), "pre pad channels not +0"
-    print(f"worst err/tol {net.op} pre: {worst:.3f}")
-
-
-def check_conv(net, name, tensors=None):
-    sp_ = net.specs[name]
-    node = net.node(name)
-    x = M.source_of(node, {node[2][0]: net.tap(node[2][0])}, net.specs)
-    got = net.tap(name)
-    ref, mag = M.layer_ref(sp_, x, tensors or net.ts)
-    assert got.shape[:3] == ref.shape[:3], (name, got.shape, ref.shape)
-    assert got.shape[3] == -(-sp_["out_c"] // 64) * 64
-    tol = M.layer_tolerance(sp_, ref, mag)
-    worst = []
-    for f in range(len(FRAMES)):  # frame 1 always, frame 0 as well
-        worst.append(R.assert_within(got[f, ..., :sp_["out_c"]], ref[f],
-                                     tol[f], f"{net.op} {name} frame {f}"))
-    pad = got[..., sp_["out_c"]:]
-    assert not pad.view(np.uint32).any(), \
-        f"{net.op} {name}: pad columns >= {sp_['out_c']} are not +0"
-    print(f"worst err/tol {net.op} {name}: frame 0 {worst[0]:.3f}, "
-          f"frame 1 {worst[1]:.3f}")
 
 
 def keypoints_of(rows):

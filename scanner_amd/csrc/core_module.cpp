@@ -25,6 +25,7 @@
 #include "ops/jpeg_common.h"
 #include "ops/jpeg_sync_common.h"
 #include "ops/kernel.h"
+#include "ops/png_common.h"
 #include "ops/python_kernel.h"
 #include "video/svc.h"
 
@@ -1097,6 +1098,168 @@ PYBIND11_MODULE(_core, m) {
         py::arg("h"), py::arg("w"), py::arg("c"), py::arg("quality") = 90,
         py::arg("batch") = 8, py::arg("iters") = 1, py::arg("mode") = "gpu",
         py::arg("clip") = "smooth", py::arg("subsampling") = "444");
+  // ---- PNG encode (ops/image_encoder.cpp, ops/png_encode_cpu.cpp,
+  // kernels/png_encode.hip)
+  m.def("png_chunk_bytes", []() { return kPngChunkBytes; });
+  m.def("png_size_bound", [](i32 h, i32 w, i32 c) {
+    png_check_args(h, w, c);
+    return png_size_bound(h, w, c);
+  }, py::arg("h"), py::arg("w"), py::arg("c"));
+  // one [H,W,C] u8 frame -> file bytes, writer = "zlib" | "parallel"
+  m.def("png_cpu_encode",
+        [](py::array_t<u8, py::array::c_style | py::array::forcecast> frame,
+           const std::string& writer) {
+          SCA_CHECK(frame.ndim() == 3, "frame must be [H,W,C]");
+          i32 h = (i32)frame.shape(0), w = (i32)frame.shape(1),
+              c = (i32)frame.shape(2);
+          auto v = png_parse_writer(writer) == PngWriter::kParallel
+                       ? png_encode_parallel_cpu(frame.data(), h, w, c)
+                       : encode_png(frame.data(), h, w, c);
+          return py::bytes((const char*)v.data(), v.size());
+        },
+        py::arg("frame"), py::arg("writer") = "zlib");
+  // a list of [H,W,C] u8 frames, shapes may differ -> list of file bytes
+  // ("parallel" writer). Every frame is uploaded on its own; consecutive
+  // frames of one shape are encoded in one call, as the op does.
+  m.def("png_gpu_encode", [](py::list frames) {
+    SCA_CHECK(have_gpu(), "png_gpu_encode needs a GPU");
+    using Arr = py::array_t<u8, py::array::c_style | py::array::forcecast>;
+    DeviceHandle dev{DeviceType::GPU, 0};
+    std::vector<Arr> arrs;
+    for (py::handle f : frames) {
+      arrs.push_back(f.cast<Arr>());
+      SCA_CHECK(arrs.back().ndim() == 3, "frames must be [H,W,C]");
+      png_check_args((i32)arrs.back().shape(0), (i32)arrs.back().shape(1),
+                     (i32)arrs.back().shape(2));
+    }
+    std::vector<u8*> dfr, bufs;
+    std::vector<u64> sizes;
+    py::list res;
+    auto cleanup = [&]() {
+      for (u8* b : bufs) delete_buffer(dev, b);
+      for (u8* b : dfr) delete_buffer(dev, b);
+    };
+    try {
+      for (const Arr& a : arrs) {
+        dfr.push_back(new_buffer(dev, (size_t)a.size()));
+        memcpy_buffer(dfr.back(), dev, a.data(), CPU_DEVICE, (size_t)a.size());
+      }
+      size_t i = 0;
+      while (i < arrs.size()) {
+        size_t j = i + 1;
+        while (j < arrs.size() && arrs[j].shape(0) == arrs[i].shape(0) &&
+               arrs[j].shape(1) == arrs[i].shape(1) &&
+               arrs[j].shape(2) == arrs[i].shape(2))
+          ++j;
+        std::vector<const u8*> fp(dfr.begin() + i, dfr.begin() + j);
+        png_encode_gpu(fp, (i32)arrs[i].shape(0), (i32)arrs[i].shape(1),
+                       (i32)arrs[i].shape(2), dev, per_thread_hip_stream(),
+                       bufs, sizes);
+        i = j;
+      }
+      for (size_t k = 0; k < bufs.size(); ++k) {
+        std::string host(sizes[k], '\0');
+        memcpy_buffer((u8*)host.data(), CPU_DEVICE, bufs[k], dev, sizes[k]);
+        res.append(py::bytes(host));
+      }
+    } catch (...) {
+      cleanup();
+      throw;
+    }
+    cleanup();
+    return res;
+  });
+  // Seconds for `iters` encodes of `batch` device-resident h*w*c frames,
+  // each ending with the files in host memory, and the bytes of one
+  // iteration. mode "gpu": png_encode_gpu, then D2H of the files. mode
+  // "cpu-parallel": D2H of the raw frames, then png_encode_parallel_cpu.
+  // mode "zlib": D2H of the raw frames, then the zlib writer. The clips are
+  // those of jpeg_encode_bench.
+  m.def("png_encode_bench",
+        [](i32 h, i32 w, i32 c, i64 batch, i32 iters, const std::string& mode,
+           const std::string& clip) {
+          SCA_CHECK(have_gpu(), "png_encode_bench needs a GPU");
+          SCA_CHECK(mode == "gpu" || mode == "cpu-parallel" || mode == "zlib",
+                    "mode must be 'gpu', 'cpu-parallel' or 'zlib'");
+          SCA_CHECK(clip == "smooth" || clip == "noise",
+                    "clip must be 'smooth' or 'noise'");
+          png_check_args(h, w, c);
+          SCA_CHECK(batch > 0 && iters > 0, "empty benchmark");
+          size_t fsize = (size_t)h * w * c;
+          DeviceHandle dev{DeviceType::GPU, 0};
+          u8* d = new_block_buffer(dev, fsize * batch, 1);
+          double secs = 0;
+          u64 out_bytes = 0;
+          try {
+            {
+              std::vector<u8> host(fsize * batch);
+              u32 x = 2654435761u;
+              size_t p = 0;
+              for (i64 i = 0; i < batch; ++i)
+                for (i32 y = 0; y < h; ++y)
+                  for (i32 xx = 0; xx < w; ++xx)
+                    for (i32 ch = 0; ch < c; ++ch, ++p) {
+                      if (clip == "noise") {
+                        x ^= x << 13; x ^= x >> 17; x ^= x << 5;
+                        host[p] = (u8)(x >> 24);
+                      } else {
+                        i64 v = ch % 3 == 0   ? xx + i * 2
+                                : ch % 3 == 1 ? y + i
+                                              : (xx + y) / 2 + i * 3;
+                        host[p] = (u8)(v & 0xff);
+                      }
+                    }
+              memcpy_buffer(d, dev, host.data(), CPU_DEVICE, fsize * batch);
+            }
+            std::vector<const u8*> fp;
+            for (i64 i = 0; i < batch; ++i) fp.push_back(d + (size_t)i * fsize);
+            py::gil_scoped_release rel;
+            auto t0 = std::chrono::steady_clock::now();
+            for (i32 it = 0; it < iters; ++it) {
+              out_bytes = 0;
+              if (mode == "gpu") {
+                std::vector<u8*> bufs;
+                std::vector<u64> sizes;
+                png_encode_gpu(fp, h, w, c, dev, per_thread_hip_stream(), bufs,
+                               sizes);
+                std::vector<u8*> dst;
+                std::vector<const u8*> src(bufs.begin(), bufs.end());
+                std::vector<size_t> sz(sizes.begin(), sizes.end());
+                for (u64 s : sizes) {
+                  dst.push_back(new_buffer(CPU_DEVICE, s));
+                  out_bytes += s;
+                }
+                memcpy_vec(dst, CPU_DEVICE, src, dev, sz);
+                for (u8* b : dst) delete_buffer(CPU_DEVICE, b);
+                for (u8* b : bufs) delete_buffer(dev, b);
+              } else {
+                std::vector<u8*> dst;
+                std::vector<size_t> sz(batch, fsize);
+                for (i64 i = 0; i < batch; ++i)
+                  dst.push_back(new_buffer(CPU_DEVICE, fsize));
+                memcpy_vec(dst, CPU_DEVICE, fp, dev, sz);
+                for (i64 i = 0; i < batch; ++i) {
+                  auto v = mode == "zlib"
+                               ? encode_png(dst[i], h, w, c)
+                               : png_encode_parallel_cpu(dst[i], h, w, c);
+                  out_bytes += v.size();
+                  delete_buffer(CPU_DEVICE, dst[i]);
+                }
+              }
+            }
+            secs = std::chrono::duration<double>(
+                       std::chrono::steady_clock::now() - t0)
+                       .count();
+          } catch (...) {
+            delete_buffer(dev, d);
+            throw;
+          }
+          delete_buffer(dev, d);
+          return py::make_tuple(secs, out_bytes);
+        },
+        py::arg("h"), py::arg("w"), py::arg("c"), py::arg("batch") = 8,
+        py::arg("iters") = 1, py::arg("mode") = "gpu",
+        py::arg("clip") = "smooth");
   // ---- still-image decode (ops/jpeg_decode_cpu.cpp, ops/png_decode.cpp,
   // kernels/jpeg_decode.hip)
   auto image_to_array = [](const DecodedImage& img) {

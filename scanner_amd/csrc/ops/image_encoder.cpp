@@ -3,7 +3,9 @@
 // backed by lodepng/OpenCV). PNG: a from-scratch writer over the system
 // zlib (deflate of filter-0 scanlines). JPEG: the baseline encoder of
 // jpeg_cpu.cpp. Both take gray (1ch) and RGB (3ch) u8 frames. This is the
-// CPU kernel; the GPU kernel (JPEG only) lives in kernels/jpeg_encode.hip.
+// CPU kernel; the GPU kernel lives in kernels/jpeg_encode.hip. PNG has a
+// second writer, png_writer="parallel" (png_common.h, png_encode_cpu.cpp),
+// which the GPU kernel writes too.
 #include <zlib.h>
 
 #include <cstring>
@@ -13,6 +15,7 @@
 #include "../msgpack.h"
 #include "jpeg_common.h"
 #include "kernel.h"
+#include "png_common.h"
 
 namespace sca {
 
@@ -91,6 +94,9 @@ class ImageEncoderKernelCPU : public BatchedKernel {
     // like quality, read for JPEG only
     if (format_ != "png")
       subsampling_ = jpeg_parse_subsampling(a.get_str("subsampling", "444"));
+    // read for PNG only
+    if (format_ == "png")
+      png_writer_ = png_parse_writer(a.get_str("png_writer", "zlib"));
   }
   void execute_batch(const BatchedElements& in, BatchedElements& out) override {
     for (const Element& f : in[0]) {
@@ -98,10 +104,12 @@ class ImageEncoderKernelCPU : public BatchedKernel {
                 "ImageEncoder needs u8 frames");
       i32 h = f.frame_info.shape[0], w = f.frame_info.shape[1],
           c = f.frame_info.shape[2];
-      auto blob = format_ == "png"
-                      ? encode_png(f.buffer, h, w, c)
-                      : jpeg_encode_cpu(f.buffer, h, w, c, quality_,
-                                        subsampling_);
+      auto blob = format_ != "png"
+                      ? jpeg_encode_cpu(f.buffer, h, w, c, quality_,
+                                        subsampling_)
+                  : png_writer_ == PngWriter::kParallel
+                      ? png_encode_parallel_cpu(f.buffer, h, w, c)
+                      : encode_png(f.buffer, h, w, c);
       Element e;
       e.size = blob.size();
       e.buffer = new_buffer(config_.device, e.size);
@@ -115,6 +123,7 @@ class ImageEncoderKernelCPU : public BatchedKernel {
   std::string format_;
   i32 quality_;
   JpegSubsampling subsampling_ = JpegSubsampling::k444;
+  PngWriter png_writer_ = PngWriter::kZlib;
 };
 
 }  // namespace

@@ -46,6 +46,7 @@
 #include "../csrc/msgpack.h"
 #include "../csrc/ops/jpeg_common.h"
 #include "../csrc/ops/kernel.h"
+#include "../csrc/ops/png_common.h"
 
 namespace sca {
 
@@ -503,16 +504,24 @@ void jpeg_encode_gpu(const std::vector<const u8*>& frames, i32 h, i32 w,
 
 namespace {
 
-// ImageEncoder on the GPU: JPEG only (PNG's deflate stays a CPU kernel).
+// ImageEncoder on the GPU: JPEG, and PNG with png_writer="parallel"
+// (kernels/png_encode.hip); the zlib PNG writer stays a CPU kernel.
 class ImageEncoderKernelGPU : public BatchedKernel {
  public:
   explicit ImageEncoderKernelGPU(const KernelConfig& cfg)
       : BatchedKernel(cfg) {
     auto a = mp::decode(cfg.args);
     std::string format = a.get_str("format", "png");
-    SCA_CHECK(format != "png",
-              "ImageEncoder format=png has no GPU kernel; run it with "
-              "device=CPU (format=jpg is supported on the GPU)");
+    if (format == "png") {
+      // like subsampling for JPEG, read for PNG only
+      PngWriter writer = png_parse_writer(a.get_str("png_writer", "zlib"));
+      SCA_CHECK(writer == PngWriter::kParallel,
+                "ImageEncoder format=png has no GPU kernel; run it with "
+                "device=CPU (format=jpg is supported on the GPU), or pass "
+                "png_writer=\"parallel\"");
+      png_ = true;
+      return;
+    }
     SCA_CHECK(format == "jpg" || format == "jpeg",
               "ImageEncoder supports format=png|jpg|jpeg, got '" + format +
                   "'");
@@ -563,8 +572,13 @@ class ImageEncoderKernelGPU : public BatchedKernel {
         config_.hip_stream ? config_.hip_stream : per_thread_hip_stream();
     std::vector<u8*> bufs;
     std::vector<u64> sizes;
-    jpeg_encode_gpu(frames, fi.shape[0], fi.shape[1], fi.shape[2], quality_,
-                    config_.device, stream, bufs, sizes, subsampling_);
+    if (png_) {
+      png_encode_gpu(frames, fi.shape[0], fi.shape[1], fi.shape[2],
+                     config_.device, stream, bufs, sizes);
+    } else {
+      jpeg_encode_gpu(frames, fi.shape[0], fi.shape[1], fi.shape[2], quality_,
+                      config_.device, stream, bufs, sizes, subsampling_);
+    }
     for (size_t i = i0; i < i1; ++i) {
       Element& e = out[i];
       e.buffer = bufs[i - i0];
@@ -572,11 +586,14 @@ class ImageEncoderKernelGPU : public BatchedKernel {
       e.device = config_.device;
     }
     if (config_.profiler)
-      config_.profiler->increment("jpeg_gpu_encode_frames", (i64)(i1 - i0));
+      config_.profiler->increment(
+          png_ ? "png_gpu_encode_frames" : "jpeg_gpu_encode_frames",
+          (i64)(i1 - i0));
   }
 
-  i32 quality_;
-  JpegSubsampling subsampling_;
+  bool png_ = false;
+  i32 quality_ = 90;
+  JpegSubsampling subsampling_ = JpegSubsampling::k444;
 };
 
 }  // namespace

@@ -30,6 +30,7 @@ CPP_SOURCES = [
     "csrc/ops/jpeg_decode_cpu.cpp",
     "csrc/ops/jpeg_sync_cpu.cpp",
     "csrc/ops/png_decode.cpp",
+    "csrc/ops/png_encode_cpu.cpp",
     "csrc/ops/image_decoder.cpp",
     "csrc/ops/detector.cpp",
     "csrc/ops/files_source.cpp",
@@ -48,6 +49,7 @@ HIP_SOURCES = [
     "kernels/svc_codec.hip",
     "kernels/svc_encode.hip",
     "kernels/jpeg_encode.hip",
+    "kernels/png_encode.hip",
     "kernels/jpeg_decode.hip",
     "kernels/jpeg_sync_decode.hip",
     "kernels/color.hip",

@@ -1905,6 +1905,7 @@ PYBIND11_MODULE(_core, m) {
     std::string s = b;
     Mp4Track t = mp4_parse((const u8*)s.data(), s.size());
     py::dict d;
+    d["codec"] = t.codec;
     d["width"] = t.width;
     d["height"] = t.height;
     d["length_size"] = t.length_size;
@@ -1930,8 +1931,16 @@ PYBIND11_MODULE(_core, m) {
         [](std::shared_ptr<Database> db, const std::string& name,
            const std::string& column,
            py::array_t<u8, py::array::c_style | py::array::forcecast> frames,
-           i64 io_packet_size, const std::string& codec) {
+           i64 io_packet_size, const std::string& codec, i32 quality,
+           const std::string& subsampling) {
           SCA_CHECK(frames.ndim() == 4, "frames must be [N,H,W,C] u8");
+          MjpegOptions mjpeg_opt;
+          if (codec == "mjpeg") {
+            mjpeg_opt.quality = quality;
+            mjpeg_opt.subsampling = jpeg_parse_subsampling(subsampling);
+            jpeg_check_args((i32)frames.shape(1), (i32)frames.shape(2),
+                            (i32)frames.shape(3), quality);
+          }
           i64 n = frames.shape(0);
           i32 h = (i32)frames.shape(1), w = (i32)frames.shape(2),
               c = (i32)frames.shape(3);
@@ -1973,6 +1982,11 @@ PYBIND11_MODULE(_core, m) {
               svc_encode_cpu(data + (size_t)s * fsize, e - s, h, w, c,
                              /*gop=*/16, stream, vm);
               write_video_item(*db, t, column, item, stream, vm);
+            } else if (codec == "mjpeg") {
+              std::vector<u8> stream;
+              mjpeg_encode_cpu(data + (size_t)s * fsize, e - s, h, w, c,
+                               mjpeg_opt, stream, vm);
+              write_video_item(*db, t, column, item, stream, vm);
             } else {
               throw ScannerError("unknown codec '" + codec + "'");
             }
@@ -1984,7 +1998,252 @@ PYBIND11_MODULE(_core, m) {
           db->commit_table(t.id);
         },
         py::arg("db"), py::arg("name"), py::arg("column"), py::arg("frames"),
-        py::arg("io_packet_size") = 128, py::arg("codec") = "raw");
+        py::arg("io_packet_size") = 128, py::arg("codec") = "raw",
+        py::arg("quality") = 90,
+        py::arg("subsampling") = kMjpegDefaultSubsampling);
+
+  // ---- Motion-JPEG (video/mjpeg.h, kernels/mjpeg_index.hip) ----
+  // The restart-segment index of samples [offsets[i], +sizes[i]) of
+  // `stream`. The reference header is the first header_len bytes of sample
+  // 0; its geometry and restart interval give the MCUs per segment, nseg is
+  // the caller's. Returns (segments [n, nseg, 4] u32, status [n] u32);
+  // segments are offsets into `stream` and zero for a sample with a status.
+  auto mjpeg_index_setup = [](const std::string& s,
+                              const std::vector<u64>& offsets,
+                              const std::vector<u64>& sizes, u32 header_len,
+                              u32 nseg, MjpegIndexParams& p) {
+    SCA_CHECK(!offsets.empty() && offsets.size() == sizes.size(),
+              "one size per offset, at least one sample");
+    for (size_t i = 0; i < offsets.size(); ++i)
+      SCA_CHECK(offsets[i] <= s.size() && sizes[i] <= s.size() - offsets[i],
+                "sample " + std::to_string(i) + " lies outside the stream");
+    SCA_CHECK(header_len <= sizes[0], "header_len exceeds sample 0");
+    SCA_CHECK(nseg >= 1, "nseg must be at least 1");
+    auto ref =
+        mjpeg_ref_header((const u8*)s.data() + offsets[0], sizes[0]);
+    SCA_CHECK(ref->params.header_len == header_len,
+              "header_len is not where the scan of sample 0 starts (" +
+                  std::to_string(ref->params.header_len) + ")");
+    p = ref->params;
+    p.nseg = nseg;
+  };
+  auto mjpeg_index_result = [](const std::vector<MjpegSeg>& segs,
+                               const std::vector<u32>& status, u32 nseg) {
+    py::array_t<u32> sa({(i64)status.size(), (i64)nseg, (i64)4});
+    std::memcpy(sa.mutable_data(), segs.data(), segs.size() * sizeof(MjpegSeg));
+    py::array_t<u32> st({(i64)status.size()});
+    std::memcpy(st.mutable_data(), status.data(), status.size() * 4);
+    return py::make_tuple(sa, st);
+  };
+  m.def("mjpeg_index_ref",
+        [mjpeg_index_setup, mjpeg_index_result](
+            py::bytes stream, std::vector<u64> offsets, std::vector<u64> sizes,
+            u32 header_len, u32 nseg) {
+          std::string s = stream;
+          MjpegIndexParams p;
+          mjpeg_index_setup(s, offsets, sizes, header_len, nseg, p);
+          const u8* ref = (const u8*)s.data() + offsets[0];
+          size_t n = offsets.size();
+          std::vector<MjpegSeg> segs(n * nseg, MjpegSeg{0, 0, 0, 0});
+          std::vector<u32> status(n, 0);
+          for (size_t i = 0; i < n; ++i) {
+            status[i] = mjpeg_index_ref((const u8*)s.data() + offsets[i],
+                                        sizes[i], ref, p, (u32)offsets[i],
+                                        segs.data() + i * nseg);
+            if (status[i] != kMjpegOk)
+              std::fill(segs.begin() + i * nseg, segs.begin() + (i + 1) * nseg,
+                        MjpegSeg{0, 0, 0, 0});
+          }
+          return mjpeg_index_result(segs, status, nseg);
+        },
+        py::arg("stream"), py::arg("offsets"), py::arg("sizes"),
+        py::arg("header_len"), py::arg("nseg"));
+  m.def("mjpeg_index_gpu",
+        [mjpeg_index_setup, mjpeg_index_result](
+            py::bytes stream, std::vector<u64> offsets, std::vector<u64> sizes,
+            u32 header_len, u32 nseg) {
+          SCA_CHECK(have_gpu(), "mjpeg_index_gpu needs a GPU");
+          std::string s = stream;
+          MjpegIndexParams p;
+          mjpeg_index_setup(s, offsets, sizes, header_len, nseg, p);
+          std::vector<MjpegSeg> segs;
+          std::vector<u32> status;
+          mjpeg_index_gpu((const u8*)s.data(), s.size(), offsets, sizes,
+                          (const u8*)s.data() + offsets[0], p, segs, status);
+          return mjpeg_index_result(segs, status, nseg);
+        },
+        py::arg("stream"), py::arg("offsets"), py::arg("sizes"),
+        py::arg("header_len"), py::arg("nseg"));
+  // Header length, segment count and restart interval of a JPEG file, as
+  // the codec derives them from a reference header.
+  m.def("mjpeg_header_info", [](py::bytes blob) {
+    std::string s = blob;
+    auto ref = mjpeg_ref_header((const u8*)s.data(), s.size());
+    py::dict d;
+    d["header_len"] = ref->params.header_len;
+    d["nseg"] = ref->params.nseg;
+    d["mcus_per_seg"] = ref->params.mcus_per_seg;
+    d["nmcu"] = ref->params.nmcu;
+    d["has_dri"] = ref->device_ok;
+    return d;
+  });
+  // Timing of the two GPU decode paths of an mjpeg stream (tools/
+  // bench_mjpeg.py): "index" decodes from a device-resident copy with the
+  // device-side index (mjpeg_decode_gpu_dev); "host" is the still-image
+  // path, jpeg_parse of every sample on the host and jpeg_decode_gpu, which
+  // uploads the entropy bytes; "index_kernel" is the index kernel alone.
+  // The modes alternate window by window in this one process, each window
+  // ends synchronised, the first `warmup` windows of each are dropped.
+  // Returns {mode: [seconds per window]}.
+  m.def("mjpeg_decode_bench",
+        [](py::bytes stream, std::vector<u64> offsets, std::vector<u64> sizes,
+           i32 h, i32 w, i32 c, int windows, int warmup) {
+          SCA_CHECK(have_gpu(), "mjpeg_decode_bench needs a GPU");
+          std::string s = stream;
+          size_t n = offsets.size();
+          SCA_CHECK(n > 0 && sizes.size() == n, "one size per offset");
+          VideoMetadata vm;
+          vm.codec = "mjpeg";
+          vm.height = h;
+          vm.width = w;
+          vm.channels = c;
+          vm.num_frames = (i64)n;
+          vm.sample_offsets = offsets;
+          vm.sample_sizes = sizes;
+          std::vector<i64> want;
+          for (size_t i = 0; i < n; ++i) {
+            SCA_CHECK(offsets[i] <= s.size() &&
+                          sizes[i] <= s.size() - offsets[i],
+                      "sample " + std::to_string(i) +
+                          " lies outside the stream");
+            want.push_back((i64)i);
+          }
+          const u8* base = (const u8*)s.data();
+          auto ref = mjpeg_ref_header(base + offsets[0], sizes[0]);
+          DeviceHandle dev{DeviceType::GPU, 0};
+          u8* d = new_buffer(dev, s.size());
+          std::vector<double> t_index, t_host, t_kernel;
+          try {
+            memcpy_buffer(d, dev, base, CPU_DEVICE, s.size());
+            auto now = [] { return std::chrono::steady_clock::now(); };
+            auto secs = [](auto a, auto b) {
+              return std::chrono::duration<double>(b - a).count();
+            };
+            for (int it = 0; it < windows + warmup; ++it) {
+              auto t0 = now();
+              MjpegGpuStats st;
+              auto elems =
+                  mjpeg_decode_gpu_dev(d, 0, vm, want, dev, *ref, &st);
+              auto t1 = now();
+              for (auto& e : elems) delete_buffer(dev, e.buffer);
+              SCA_CHECK(st.fallback_frames == 0,
+                        "mjpeg_decode_bench: frames fell back");
+              auto t2 = now();
+              std::vector<ImageBlob> blobs(n);
+              std::vector<JpegInfo> infos(n);
+              for (size_t i = 0; i < n; ++i) {
+                blobs[i] = {base + offsets[i], (size_t)sizes[i]};
+                infos[i] = jpeg_parse(blobs[i].data, blobs[i].size);
+              }
+              std::vector<DeviceFrame> frames;
+              jpeg_decode_gpu(blobs, infos, dev, per_thread_hip_stream(),
+                              frames);
+              auto t3 = now();
+              for (auto& f : frames) delete_buffer(dev, f.buffer);
+              std::vector<MjpegSeg> segs;
+              std::vector<u32> status;
+              double ms = 0;
+              mjpeg_index_gpu(base, s.size(), offsets, sizes,
+                              base + offsets[0], ref->params, segs, status,
+                              &ms, 1);
+              if (it >= warmup) {
+                t_index.push_back(secs(t0, t1));
+                t_host.push_back(secs(t2, t3));
+                t_kernel.push_back(ms * 1e-3);
+              }
+            }
+          } catch (...) {
+            delete_buffer(dev, d);
+            throw;
+          }
+          delete_buffer(dev, d);
+          py::dict out;
+          out["index"] = t_index;
+          out["host"] = t_host;
+          out["index_kernel"] = t_kernel;
+          return out;
+        },
+        py::arg("stream"), py::arg("offsets"), py::arg("sizes"), py::arg("h"),
+        py::arg("w"), py::arg("c"), py::arg("windows") = 10,
+        py::arg("warmup") = 3);
+  // mjpeg_decode_gpu on samples laid out in `stream` (an item's bytes):
+  // frames `want`, decoded from a device copy of the stream. Returns
+  // (frames [n,H,W,C] u8, index_frames, fallback_frames).
+  m.def("mjpeg_gpu_decode",
+        [](py::bytes stream, std::vector<u64> offsets, std::vector<u64> sizes,
+           std::vector<i64> want, i32 h, i32 w, i32 c) {
+          SCA_CHECK(have_gpu(), "mjpeg_gpu_decode needs a GPU");
+          std::string s = stream;
+          SCA_CHECK(!offsets.empty() && offsets.size() == sizes.size(),
+                    "one size per offset, at least one sample");
+          VideoMetadata vm;
+          vm.codec = "mjpeg";
+          vm.height = h;
+          vm.width = w;
+          vm.channels = c;
+          vm.num_frames = (i64)offsets.size();
+          vm.sample_offsets = offsets;
+          vm.sample_sizes = sizes;
+          for (size_t i = 0; i < offsets.size(); ++i) {
+            SCA_CHECK(offsets[i] <= s.size() &&
+                          sizes[i] <= s.size() - offsets[i],
+                      "sample " + std::to_string(i) +
+                          " lies outside the stream");
+            vm.keyframe_indices.push_back((i64)i);
+          }
+          std::shared_ptr<const MjpegRefHeader> ref;
+          try {
+            ref = mjpeg_ref_header((const u8*)s.data() + offsets[0], sizes[0]);
+          } catch (const ScannerError&) {
+            ref = std::make_shared<MjpegRefHeader>();
+          }
+          DeviceHandle dev{DeviceType::GPU, 0};
+          MjpegGpuStats st;
+          auto elems = mjpeg_decode_gpu((const u8*)s.data(), s.size(), vm, want,
+                                        dev, *ref, 0, &st);
+          size_t fsize = (size_t)h * w * c;
+          py::array_t<u8> out({(i64)elems.size(), (i64)h, (i64)w, (i64)c});
+          for (size_t i = 0; i < elems.size(); ++i) {
+            memcpy_buffer(out.mutable_data() + i * fsize, CPU_DEVICE,
+                          elems[i].buffer, dev, fsize);
+            delete_buffer(dev, elems[i].buffer);
+          }
+          return py::make_tuple(out, st.index_frames, st.fallback_frames);
+        },
+        py::arg("stream"), py::arg("offsets"), py::arg("sizes"),
+        py::arg("want"), py::arg("h"), py::arg("w"), py::arg("c"));
+
+  // One item of a video column as stored: (bytes, video metadata).
+  m.def("read_video_item",
+        [](std::shared_ptr<Database> db, const std::string& table,
+           const std::string& column, i32 item) {
+          TableMetadata t = db->get_table(table);
+          VideoMetadata vm = read_video_metadata(*db, t, column, item);
+          auto bytes = db->storage()->read_all(
+              db->paths().item(t.id, t.column_id(column), item));
+          py::dict d;
+          d["codec"] = vm.codec;
+          d["height"] = vm.height;
+          d["width"] = vm.width;
+          d["channels"] = vm.channels;
+          d["frame_type"] = (i32)vm.frame_type;
+          d["num_frames"] = vm.num_frames;
+          d["keyframe_indices"] = vm.keyframe_indices;
+          d["sample_offsets"] = vm.sample_offsets;
+          d["sample_sizes"] = vm.sample_sizes;
+          return py::make_tuple(
+              py::bytes((const char*)bytes.data(), bytes.size()), d);
+        });
 
   m.def("read_column",
         [](std::shared_ptr<Database> db, const std::string& table,
@@ -2022,7 +2281,12 @@ PYBIND11_MODULE(_core, m) {
                 auto stream = db->storage()->read_all(
                     db->paths().item(t.id, t.column_id(column), ir.item));
                 std::vector<std::vector<u8>> frames;
-                svc_decode_cpu(stream.data(), stream.size(), vm, want, frames);
+                if (vm.codec == "mjpeg")
+                  mjpeg_decode_cpu(stream.data(), stream.size(), vm, want,
+                                   frames);
+                else
+                  svc_decode_cpu(stream.data(), stream.size(), vm, want,
+                                 frames);
                 for (auto& fb : frames) {
                   py::tuple shape =
                       py::make_tuple(vm.height, vm.width, vm.channels);

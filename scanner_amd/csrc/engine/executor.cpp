@@ -45,7 +45,8 @@ bool read_svc_gpu_encode_switch() {
 // one retained reference to the last frame of the previous packet — the
 // prediction source of the next packet's first delta frame.
 struct SinkSvcEncode {
-  bool candidate = false;  // compress=svc, Video column, table sink
+  bool candidate = false;  // compress=svc|mjpeg, Video column, table sink
+  bool mjpeg = false;      // the column's codec is mjpeg, else svc
   bool decided = false;    // device fixed at the column's first packet
   bool on_gpu = false;
   DeviceHandle dev{DeviceType::CPU, 0};
@@ -83,6 +84,7 @@ LocalExecutor::LocalExecutor(std::shared_ptr<Database> db, JobGraph graph,
   mc.gpu_ids = gpu_ids_;
   init_memory_allocators(mc);
   svc_gpu_encode_ = read_svc_gpu_encode_switch();
+  mjpeg_gpu_ = read_mjpeg_gpu_switch();
   db_key_ = std::hash<std::string>{}(db_->paths().root);
   if (!gpu_ids_.empty()) {
     size_t budget = pp_.span_cache_size;
@@ -349,6 +351,66 @@ SpanHandle LocalExecutor::acquire_ready_span(const TableMetadata& table,
   return res.first;
 }
 
+namespace {
+
+// Byte range [lo, hi) of an item that the wanted item-local frames need:
+// svc decodes keyframe-aligned spans, mjpeg only the wanted samples, so its
+// range runs from the first wanted sample to the end of the last. False
+// when nothing is wanted.
+bool codec_decode_range(const VideoMetadata& m, const std::vector<i64>& local,
+                        u64& lo, u64& hi) {
+  if (m.codec == "mjpeg") {
+    if (local.empty()) return false;
+    for (i64 f : local)
+      SCA_CHECK(f >= 0 && (size_t)f < m.sample_offsets.size(),
+                "mjpeg: frame " + std::to_string(f) + " is not in the item");
+    lo = m.sample_offsets[local.front()];
+    hi = m.sample_offsets[local.back()] + m.sample_sizes[local.back()];
+    return true;
+  }
+  std::vector<i64> span = svc_decode_span(m, local);
+  if (span.empty()) return false;
+  lo = m.sample_offsets[span.front()];
+  hi = m.sample_offsets[span.back()] + m.sample_sizes[span.back()];
+  return true;
+}
+
+}  // namespace
+
+std::shared_ptr<const MjpegRefHeader> LocalExecutor::mjpeg_ref_for(
+    const TableMetadata& table, const std::string& column, i32 item,
+    const VideoMetadata& vm) {
+  auto key = std::make_tuple(table.id, table.column_id(column), item);
+  {
+    std::lock_guard<std::mutex> l(mjpeg_ref_mu_);
+    auto it = mjpeg_refs_.find(key);
+    if (it != mjpeg_refs_.end()) return it->second;
+  }
+  std::shared_ptr<const MjpegRefHeader> ref;
+  if (!vm.sample_sizes.empty()) {
+    std::string path =
+        db_->paths().item(table.id, table.column_id(column), item);
+    u64 want = std::min<u64>(vm.sample_sizes[0], kMjpegHeaderReadBytes);
+    for (int attempt = 0; attempt < 2 && !ref; ++attempt) {
+      std::vector<u8> head(want);
+      db_->storage()->read_range(path, vm.sample_offsets[0], want,
+                                 head.data());
+      try {
+        ref = mjpeg_ref_header(head.data(), head.size());
+      } catch (const ScannerError&) {
+        // a header longer than the first read, or a sample 0 that does not
+        // parse: try the whole sample once, then leave every frame to the
+        // serial path, which reports what is wrong with the frames it meets
+        if (want == vm.sample_sizes[0]) break;
+        want = vm.sample_sizes[0];
+      }
+    }
+  }
+  if (!ref) ref = std::make_shared<MjpegRefHeader>();
+  std::lock_guard<std::mutex> l(mjpeg_ref_mu_);
+  return mjpeg_refs_.emplace(key, ref).first->second;
+}
+
 // Load-worker half of a task (runs on the prefetch pool): derive the plan
 // and read every svc video source span into pinned memory so the pipeline
 // instance starts with its input bytes already resident.
@@ -379,11 +441,9 @@ std::shared_ptr<PreparedTask> LocalExecutor::prepare_task(const TaskDesc& t,
         local.push_back(rows[ri] - ir.row_start);
         ++ri;
       }
-      if (m.codec != "svc") continue;
-      std::vector<i64> span = svc_decode_span(m, local);
-      if (span.empty()) continue;
-      u64 lo = m.sample_offsets[span.front()];
-      u64 hi = m.sample_offsets[span.back()] + m.sample_sizes[span.back()];
+      if (m.codec != "svc" && m.codec != "mjpeg") continue;
+      u64 lo = 0, hi = 0;
+      if (!codec_decode_range(m, local, lo, hi)) continue;
       PreparedTask::Span sp;
       sp.op = op_idx;
       sp.item = ir.item;
@@ -393,7 +453,7 @@ std::shared_ptr<PreparedTask> LocalExecutor::prepare_task(const TaskDesc& t,
       // H2D; a fresh insert does read+upload HERE on the load worker, off
       // the pipeline instances' critical path (overlap
       // IO/H2D with GPU compute).
-      if (!gpu_ids_.empty()) {
+      if (!gpu_ids_.empty() && (m.codec == "svc" || mjpeg_gpu_)) {
         DeviceHandle tgt{DeviceType::GPU,
                          gpu_ids_[t.task % (i32)gpu_ids_.size()]};
         sp.cached = acquire_ready_span(table, src.column, ir.item, lo, hi,
@@ -469,7 +529,7 @@ void LocalExecutor::init_sources(
                       "hardware decoder (not in this image). Export it "
                       "with save_mp4() or transcode to codec='svc'. "
                       "Decoder slot: csrc/video/ingest.h");
-        any_svc |= kv2.second.codec == "svc";
+        any_svc |= kv2.second.codec == "svc" || kv2.second.codec == "mjpeg";
       }
       if (any_svc) {
         // Codec path (decoder-automaton parity): set up per-item decode
@@ -487,10 +547,15 @@ void LocalExecutor::init_sources(
             st.local.push_back(rows[ri] - ir.row_start);
             ++ri;
           }
-          std::vector<i64> span = svc_decode_span(m, st.local);
-          if (span.empty()) continue;
-          st.lo = m.sample_offsets[span.front()];
-          st.hi = m.sample_offsets[span.back()] + m.sample_sizes[span.back()];
+          SCA_CHECK(m.codec == "svc" || m.codec == "mjpeg",
+                    "unknown video codec '" + m.codec + "'");
+          if (!codec_decode_range(m, st.local, st.lo, st.hi)) continue;
+          // mjpeg with SCANNER_MJPEG_GPU=0 decodes on the host, from host
+          // bytes, also on a GPU instance
+          const bool on_device =
+              inst.gpu.is_gpu() && (m.codec == "svc" || mjpeg_gpu_);
+          if (m.codec == "mjpeg" && on_device)
+            st.ref = mjpeg_ref_for(table, src.column, ir.item, m);
           // Device-resident bytes first (prefetched by the load worker or
           // resident from an earlier task), then prefetched host bytes,
           // then cache-fill / storage read.
@@ -498,12 +563,12 @@ void LocalExecutor::init_sources(
               prep ? prep->take_cached(op_idx, ir.item, st.lo, st.hi)
                    : nullptr;
           if (st.cached &&
-              (!inst.gpu.is_gpu() || st.cached->dev.id != inst.gpu.id)) {
+              (!on_device || st.cached->dev.id != inst.gpu.id)) {
             st.cached.reset();  // prefetched for a different GPU
           }
           st.host =
               prep ? prep->take_span(op_idx, ir.item, st.lo, st.hi) : nullptr;
-          if (!st.cached && inst.gpu.is_gpu()) {
+          if (!st.cached && on_device) {
             st.cached = acquire_ready_span(table, src.column, ir.item, st.lo,
                                            st.hi, inst.gpu, inst.profiler,
                                            st.host);
@@ -563,7 +628,43 @@ void LocalExecutor::advance_svc_source(Instance& inst,
     std::vector<i64> want(st.local.begin() + st.cursor,
                           st.local.begin() + k);
     st.cursor = k;
-    if (st.cached) {
+    if (st.vm.codec == "mjpeg") {
+      inst.profiler->increment("decoded_frames", (i64)want.size());
+      if (st.ref) {
+        Profiler::Scope sd(inst.profiler, "decode:gpu");
+        MjpegGpuStats ms;
+        auto elems =
+            st.cached
+                ? mjpeg_decode_gpu_dev(st.cached->ptr, st.lo, st.vm, want,
+                                       inst.gpu, *st.ref, &ms)
+                : mjpeg_decode_gpu(st.host, st.hi - st.lo, st.vm, want,
+                                   inst.gpu, *st.ref, st.lo, &ms);
+        inst.profiler->increment("mjpeg_gpu_index_frames", ms.index_frames);
+        inst.profiler->increment("mjpeg_host_fallback_frames",
+                                 ms.fallback_frames);
+        for (auto& e : elems) {
+          e.index += st.row_start;
+          outs[op_idx][col][e.index] = e;
+        }
+      } else {
+        Profiler::Scope sd(inst.profiler, "decode:cpu");
+        std::vector<std::vector<u8>> frames;
+        mjpeg_decode_cpu(st.host, st.hi - st.lo, st.vm, want, frames, st.lo);
+        for (size_t q = 0; q < want.size(); ++q) {
+          Element e;
+          e.is_frame = true;
+          e.frame_info.shape[0] = st.vm.height;
+          e.frame_info.shape[1] = st.vm.width;
+          e.frame_info.shape[2] = st.vm.channels;
+          e.frame_info.type = st.vm.frame_type;
+          e.size = frames[q].size();
+          e.buffer = new_buffer(CPU_DEVICE, e.size);
+          std::memcpy(e.buffer, frames[q].data(), e.size);
+          e.index = want[q] + st.row_start;
+          outs[op_idx][col][e.index] = e;
+        }
+      }
+    } else if (st.cached) {
       Profiler::Scope sd(inst.profiler, "decode:gpu");
       inst.profiler->increment("decoded_frames", (i64)want.size());
       auto elems = svc_decode_gpu_dev(st.cached->ptr, st.lo, st.vm, want,
@@ -806,6 +907,8 @@ void LocalExecutor::process_task(Instance& inst, const TaskDesc& t,
     // reference compressed-output columns + PostEvaluateWorker encode,
     // evaluate_worker.cpp:1329-1560).
     std::map<std::string, std::string> compress;
+    // options of the columns that have some (the sibling map compress_opts)
+    std::map<std::string, MjpegOptions> mjpeg_opts;
     if (!out_op.args.empty()) {
       auto a = mp::decode(out_op.args);
       auto& am = a.as_map();
@@ -814,15 +917,42 @@ void LocalExecutor::process_task(Instance& inst, const TaskDesc& t,
         for (auto& kv : cit->second.as_map())
           compress[kv.first] = kv.second.as_str();
       }
+      auto oit = am.find("compress_opts");
+      if (oit != am.end()) {
+        for (auto& kv : oit->second.as_map()) {
+          auto cmp = compress.find(kv.first);
+          SCA_CHECK(cmp != compress.end(),
+                    "compress_opts names column '" + kv.first +
+                        "', which is not compressed");
+          MjpegOptions mo;
+          for (auto& okv : kv.second.as_map()) {
+            if (cmp->second == "mjpeg" && okv.first == "quality") {
+              mo.quality = (i32)okv.second.as_int();
+              SCA_CHECK(mo.quality >= 1 && mo.quality <= 100,
+                        "mjpeg quality must be in 1..100, got " +
+                            std::to_string(mo.quality));
+            } else if (cmp->second == "mjpeg" && okv.first == "subsampling") {
+              mo.subsampling = jpeg_parse_subsampling(okv.second.as_str());
+            } else {
+              throw ScannerError("unknown option '" + okv.first +
+                                 "' for sink codec '" + cmp->second + "'");
+            }
+          }
+          mjpeg_opts[kv.first] = mo;
+        }
+      }
     }
-    if (svc_gpu_encode_ && job.sink.sink.empty() && inst.gpu.is_gpu()) {
+    if (job.sink.sink.empty() && inst.gpu.is_gpu()) {
       const TableMetadata& table = out_tables_[t.job];
       for (size_t c = 0; c < sink_enc.size() && c < table.columns.size();
            ++c) {
         auto cmp = compress.find(table.columns[c].name);
-        sink_enc[c].candidate = cmp != compress.end() &&
-                                cmp->second == "svc" &&
-                                table.columns[c].type == ColumnType::Video;
+        if (cmp == compress.end() ||
+            table.columns[c].type != ColumnType::Video)
+          continue;
+        sink_enc[c].mjpeg = cmp->second == "mjpeg";
+        sink_enc[c].candidate = (cmp->second == "svc" && svc_gpu_encode_) ||
+                                (cmp->second == "mjpeg" && mjpeg_gpu_);
       }
     }
 
@@ -936,6 +1066,71 @@ void LocalExecutor::process_task(Instance& inst, const TaskDesc& t,
               }
               SCA_CHECK(enc.decided,
                         "cannot codec-compress a column with null rows");
+            }
+            if (enc.on_gpu && enc.mjpeg) {
+              // one JPEG file per row, encoded on the device; only the
+              // files and their sizes cross the host link
+              MjpegOptions mo;
+              auto moit = mjpeg_opts.find(out_tables_[t.job].columns[c].name);
+              if (moit != mjpeg_opts.end()) mo = moit->second;
+              std::vector<const u8*> fp;
+              for (i64 row = ps; row < pe; ++row) {
+                auto pit = parent_map.find(row);
+                SCA_CHECK(pit != parent_map.end(), "sink missing row");
+                const Element& e = pit->second;
+                SCA_CHECK(!e.is_null,
+                          "cannot codec-compress a column with null rows");
+                SCA_CHECK(e.is_frame && e.frame_info.type == FrameType::U8,
+                          "mjpeg compression needs u8 frames");
+                SCA_CHECK(e.device == enc.dev,
+                          "compressed output column changed device within "
+                          "a task");
+                if (enc.vm.num_frames == 0 && fp.empty()) {
+                  enc.vm.codec = "mjpeg";
+                  enc.vm.height = e.frame_info.shape[0];
+                  enc.vm.width = e.frame_info.shape[1];
+                  enc.vm.channels = e.frame_info.shape[2];
+                  enc.vm.frame_type = FrameType::U8;
+                  jpeg_check_args(enc.vm.height, enc.vm.width,
+                                  enc.vm.channels, mo.quality);
+                }
+                SCA_CHECK(e.frame_info.shape[0] == enc.vm.height &&
+                              e.frame_info.shape[1] == enc.vm.width &&
+                              e.frame_info.shape[2] == enc.vm.channels,
+                          "mjpeg compression needs uniform frame shapes");
+                fp.push_back(e.buffer);
+              }
+              std::vector<u8*> bufs;
+              std::vector<u64> sizes;
+              jpeg_encode_gpu(fp, enc.vm.height, enc.vm.width,
+                              enc.vm.channels, mo.quality, enc.dev,
+                              per_thread_hip_stream(), bufs, sizes,
+                              mo.subsampling);
+              i64 packed = 0;
+              for (u64 sz : sizes) packed += (i64)sz;
+              size_t pos = enc.stream.size();
+              enc.stream.resize(pos + (size_t)packed);
+              std::vector<u8*> dst;
+              std::vector<const u8*> srcs(bufs.begin(), bufs.end());
+              std::vector<size_t> szs(sizes.begin(), sizes.end());
+              for (u64 sz : sizes) {
+                dst.push_back(enc.stream.data() + pos);
+                pos += (size_t)sz;
+                mjpeg_append_sample(enc.vm, sz);
+              }
+              try {
+                memcpy_vec(dst, CPU_DEVICE, srcs, enc.dev, szs);
+              } catch (...) {
+                for (u8* b : bufs) delete_buffer(enc.dev, b);
+                throw;
+              }
+              for (u8* b : bufs) delete_buffer(enc.dev, b);
+              enc.vm.num_frames += (i64)fp.size();
+              inst.profiler->increment("mjpeg_gpu_encode_frames",
+                                       (i64)fp.size());
+              inst.profiler->increment("sink_d2h_bytes",
+                                       packed + (i64)(4 * sizes.size()));
+              continue;
             }
             if (enc.on_gpu) {
               // stream-encode on the device: the raw frames never cross
@@ -1161,8 +1356,47 @@ void LocalExecutor::process_task(Instance& inst, const TaskDesc& t,
         auto cmp = compress.find(cname);
         if (cmp != compress.end() &&
             table.columns[c].type == ColumnType::Video) {
-          SCA_CHECK(cmp->second == "svc",
+          SCA_CHECK(cmp->second == "svc" || cmp->second == "mjpeg",
                     "unknown sink codec '" + cmp->second + "'");
+          if (cmp->second == "mjpeg") {
+            MjpegOptions mo;
+            auto moit = mjpeg_opts.find(cname);
+            if (moit != mjpeg_opts.end()) mo = moit->second;
+            VideoMetadata vm;
+            vm.codec = "mjpeg";
+            vm.frame_type = FrameType::U8;
+            std::vector<u8> stream;
+            for (auto& e : cols[c]) {
+              SCA_CHECK(!e.is_null,
+                        "cannot codec-compress a column with null rows");
+              SCA_CHECK(e.is_frame && e.frame_info.type == FrameType::U8,
+                        "mjpeg compression needs u8 frames");
+              if (vm.num_frames == 0) {
+                vm.height = e.frame_info.shape[0];
+                vm.width = e.frame_info.shape[1];
+                vm.channels = e.frame_info.shape[2];
+              }
+              SCA_CHECK(e.frame_info.shape[0] == vm.height &&
+                            e.frame_info.shape[1] == vm.width &&
+                            e.frame_info.shape[2] == vm.channels,
+                        "mjpeg compression needs uniform frame shapes");
+              std::vector<u8> file =
+                  jpeg_encode_cpu(e.buffer, vm.height, vm.width, vm.channels,
+                                  mo.quality, mo.subsampling);
+              stream.insert(stream.end(), file.begin(), file.end());
+              mjpeg_append_sample(vm, file.size());
+              ++vm.num_frames;
+            }
+            inst.profiler->increment("io_write_bytes", (i64)stream.size());
+            write_video_item(*db_, table, cname, t.task, stream, vm);
+            for (size_t k = 0; k < cols[c].size(); ++k) {
+              if (owned[c][k] && cols[c][k].buffer)
+                delete_buffer(CPU_DEVICE, cols[c][k].buffer);
+            }
+            cols[c].clear();
+            owned[c].clear();
+            return;
+          }
           i32 h = 0, w = 0, ch = 0;
           size_t fsize = 0;
           std::vector<u8> contig;

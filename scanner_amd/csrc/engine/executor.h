@@ -10,14 +10,18 @@
 #pragma once
 
 #include <atomic>
+#include <map>
+#include <memory>
 #include <mutex>
 #include <set>
 #include <thread>
+#include <tuple>
 
 #include "../dag/graph.h"
 #include "../ops/kernel.h"
 #include "../profiler.h"
 #include "../queue.h"
+#include "../video/mjpeg.h"
 #include "../video/span_cache.h"
 #include "table_io.h"
 
@@ -114,6 +118,8 @@ class LocalExecutor {
     SpanHandle cached;       // HBM-resident encoded bytes [lo, hi)
     u8* host = nullptr;      // pinned encoded bytes [lo, hi)
     u64 lo = 0, hi = 0;
+    // mjpeg items on a GPU instance: the header of the item's sample 0
+    std::shared_ptr<const MjpegRefHeader> ref;
   };
   void process_task(Instance& inst, const TaskDesc& t,
                     PreparedTask* prep = nullptr);
@@ -131,6 +137,11 @@ class LocalExecutor {
   void advance_svc_source(Instance& inst, std::vector<SvcItemState>& states,
                           i64 max_row, const std::string& col, OutsVec& outs,
                           i32 op_idx);
+  // The reference header of an mjpeg item, read from storage once per
+  // (table, column, item) and kept for the life of this executor.
+  std::shared_ptr<const MjpegRefHeader> mjpeg_ref_for(
+      const TableMetadata& table, const std::string& column, i32 item,
+      const VideoMetadata& vm);
   void make_instance(i32 idx);
   // Lookup-or-fill the HBM span cache for one encoded byte range; returns a
   // ready handle (device-resident bytes) or null when caching declined.
@@ -155,6 +166,12 @@ class LocalExecutor {
   // SCANNER_SVC_GPU_ENCODE as read when this executor (one job run) was
   // created: encode svc-compressed GPU output columns on the device.
   bool svc_gpu_encode_ = false;
+  // SCANNER_MJPEG_GPU, read the same way: mjpeg encode and decode on the
+  // device for GPU instances.
+  bool mjpeg_gpu_ = true;
+  std::mutex mjpeg_ref_mu_;
+  std::map<std::tuple<i32, i32, i32>, std::shared_ptr<const MjpegRefHeader>>
+      mjpeg_refs_;
 
   std::atomic<i64> tasks_done_{0};
   std::vector<std::unique_ptr<Instance>> instances_;

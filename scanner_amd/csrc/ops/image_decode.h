@@ -36,6 +36,10 @@ struct JpegInfo {
 };
 
 JpegInfo jpeg_parse(const u8* data, size_t size);
+// The first half of jpeg_parse: everything up to the start of the scan.
+// Fills every field of `info` except `segments` and returns the offset of
+// the first entropy-coded byte. Same checks, same messages.
+size_t jpeg_parse_header(const u8* data, size_t size, JpegInfo& info);
 
 struct DecodedImage {
   i32 h = 0, w = 0, c = 0;

@@ -61,12 +61,12 @@ std::string jpeg_entropy_error(u32 status, u32 segment) {
          " in restart segment " + std::to_string(segment);
 }
 
-JpegInfo jpeg_parse(const u8* data, size_t size) {
+size_t jpeg_parse_header(const u8* data, size_t size, JpegInfo& info) {
   SCA_CHECK(data != nullptr && is_jpeg(data, size),
             "not a JPEG file (no SOI marker)");
   SCA_CHECK(size < (1ull << 31), "JPEG file of 2 GiB or more");
   Reader r{data, size};
-  JpegInfo info;
+  info = JpegInfo{};
   make_zigzag(info.zz2nat);
 
   u16 qt[4][64];
@@ -197,6 +197,12 @@ JpegInfo jpeg_parse(const u8* data, size_t size) {
     std::copy(info.q[0], info.q[0] + 64, info.q[c]);
   }
   info.g = jpeg_dec_geom(h, w, nc, comp_hv[0] >> 4, comp_hv[0] & 15);
+  return scan;
+}
+
+JpegInfo jpeg_parse(const u8* data, size_t size) {
+  JpegInfo info;
+  size_t scan = jpeg_parse_header(data, size, info);
   const JpegDecGeom& g = info.g;
 
   // ---- segment index: split the entropy-coded data at RSTn ----

@@ -4,7 +4,9 @@
 #include <set>
 
 #include "../engine/table_io.h"
+#include "../ops/image_decode.h"
 #include "h264.h"
+#include "mjpeg.h"
 #include "mp4.h"
 
 namespace sca {
@@ -44,8 +46,39 @@ IngestResult ingest_video_file(Database& db, const std::string& table_name,
 
   bool is_mp4 = file.size() >= 8 && file[4] == 'f' && file[5] == 't' &&
                 file[6] == 'y' && file[7] == 'p';
-  if (is_mp4) {
-    Mp4Track t = mp4_parse(file.data(), file.size());
+  Mp4Track t;
+  if (is_mp4) t = mp4_parse(file.data(), file.size());
+  if (is_mp4 && t.codec == "mjpeg") {
+    // Motion-JPEG: the samples are stored as they are, in one item. Every
+    // one has to be a file the decoders accept, of the shape of sample 0.
+    vm.codec = "mjpeg";
+    SCA_CHECK(!t.sample_sizes.empty(), "mp4: Motion-JPEG track has no samples");
+    for (size_t s = 0; s < t.sample_sizes.size(); ++s) {
+      const u8* p = file.data() + t.sample_offsets[s];
+      try {
+        JpegInfo info = jpeg_parse(p, t.sample_sizes[s]);
+        if (s == 0) {
+          vm.height = info.g.h;
+          vm.width = info.g.w;
+          vm.channels = info.g.nc;
+        }
+        SCA_CHECK(info.g.h == vm.height && info.g.w == vm.width &&
+                      info.g.nc == vm.channels,
+                  "its shape " + std::to_string(info.g.h) + "x" +
+                      std::to_string(info.g.w) + "x" +
+                      std::to_string(info.g.nc) + " differs from sample 0's " +
+                      std::to_string(vm.height) + "x" +
+                      std::to_string(vm.width) + "x" +
+                      std::to_string(vm.channels));
+      } catch (const ScannerError& err) {
+        throw ScannerError("mjpeg ingest of " + path + ": sample " +
+                           std::to_string(s) + ": " + err.what());
+      }
+      stream.insert(stream.end(), p, p + t.sample_sizes[s]);
+      mjpeg_append_sample(vm, t.sample_sizes[s]);
+    }
+    vm.num_frames = (i64)t.sample_sizes.size();
+  } else if (is_mp4) {
     vm.width = t.width;
     vm.height = t.height;
     vm.num_frames = (i64)t.sample_sizes.size();
@@ -92,18 +125,18 @@ IngestResult ingest_video_file(Database& db, const std::string& table_name,
     stream = std::move(file);
   }
 
-  TableMetadata t =
+  TableMetadata tm =
       db.new_table(table_name, {column}, {ColumnType::Video}, true);
-  write_video_item(db, t, column, 0, stream, vm);
-  t.end_rows = {vm.num_frames};
-  db.update_table(t);
-  db.commit_table(t.id);
+  write_video_item(db, tm, column, 0, stream, vm);
+  tm.end_rows = {vm.num_frames};
+  db.update_table(tm);
+  db.commit_table(tm.id);
 
   IngestResult r;
   r.num_frames = vm.num_frames;
   r.width = vm.width;
   r.height = vm.height;
-  r.codec = "h264";
+  r.codec = vm.codec;
   return r;
 }
 
@@ -117,11 +150,23 @@ void export_mp4(Database& db, const std::string& table_name,
   std::vector<u64> offsets, sizes;
   std::vector<i64> keyframes;
   i64 row_base = 0;
+  std::string codec;
+  i32 width = 0, height = 0;
   for (i32 item = 0; item < (i32)t.end_rows.size(); ++item) {
     VideoMetadata vm = read_video_metadata(db, t, column, item);
-    SCA_CHECK(vm.codec == "h264",
+    SCA_CHECK(vm.codec == "h264" || vm.codec == "mjpeg",
               "export_mp4: column is '" + vm.codec +
-                  "', only h264-indexed tables can be remuxed");
+                  "', only h264-indexed and mjpeg tables can be remuxed");
+    if (item == 0) {
+      codec = vm.codec;
+      width = vm.width;
+      height = vm.height;
+    }
+    SCA_CHECK(vm.codec == codec, "export_mp4: the items of the column mix '" +
+                                     codec + "' and '" + vm.codec + "'");
+    SCA_CHECK(codec != "mjpeg" || (vm.width == width && vm.height == height),
+              "export_mp4: item " + std::to_string(item) +
+                  " has another frame size than item 0");
     std::vector<u8> item_bytes =
         db.storage()->read_all(db.paths().item(t.id, t.column_id(column),
                                                item));
@@ -134,11 +179,16 @@ void export_mp4(Database& db, const std::string& table_name,
     for (i64 k : vm.keyframe_indices) keyframes.push_back(row_base + k);
     row_base += vm.num_frames;
   }
-  // parameter sets are in-band — pull them from the stream's own index
-  H264Index idx = h264_index_annexb(stream.data(), stream.size());
-  std::vector<u8> mp4 =
-      mp4_write(stream.data(), stream.size(), offsets, sizes, keyframes,
-                idx.sps, idx.pps, idx.width, idx.height, fps);
+  std::vector<u8> mp4;
+  if (codec == "mjpeg") {
+    mp4 = mp4_write_mjpeg(stream.data(), stream.size(), offsets, sizes, width,
+                          height, fps);
+  } else {
+    // parameter sets are in-band — pull them from the stream's own index
+    H264Index idx = h264_index_annexb(stream.data(), stream.size());
+    mp4 = mp4_write(stream.data(), stream.size(), offsets, sizes, keyframes,
+                    idx.sps, idx.pps, idx.width, idx.height, fps);
+  }
   std::ofstream f(out_path, std::ios::binary | std::ios::trunc);
   SCA_CHECK(f.good(), "export_mp4: cannot open " + out_path);
   f.write((const char*)mp4.data(), (std::streamsize)mp4.size());

@@ -1,6 +1,7 @@
 #include "mp4.h"
 
 #include <cstring>
+#include <functional>
 
 #include "h264.h"
 
@@ -84,6 +85,36 @@ const Box* find(const std::vector<Box>& boxes, u32 type) {
   return nullptr;
 }
 
+// Length of an MPEG-4 descriptor (ISO/IEC 14496-1, 8.3.3): up to four
+// bytes of seven bits, the top bit says another follows.
+u32 descriptor_length(Cursor& c) {
+  u32 len = 0;
+  for (int i = 0; i < 4; ++i) {
+    u8 b = c.u8v();
+    len = (len << 7) | (b & 0x7fu);
+    if (!(b & 0x80u)) break;
+  }
+  return len;
+}
+
+// objectTypeIndication of an 'esds' box body: FullBox header, then
+// ES_Descriptor (tag 3) holding a DecoderConfigDescriptor (tag 4).
+u32 esds_object_type(const u8* body, size_t size) {
+  Cursor c{body, size};
+  c.skip(4, "esds header");
+  SCA_CHECK(c.u8v() == 0x03, "mp4: esds does not start with an ES_Descriptor");
+  descriptor_length(c);
+  c.skip(2, "ES_ID");
+  u8 flags = c.u8v();
+  if (flags & 0x80u) c.skip(2, "dependsOn_ES_ID");
+  if (flags & 0x40u) c.skip(c.u8v(), "ES URL");
+  if (flags & 0x20u) c.skip(2, "OCR_ES_ID");
+  SCA_CHECK(c.u8v() == 0x04,
+            "mp4: ES_Descriptor has no DecoderConfigDescriptor");
+  descriptor_length(c);
+  return c.u8v();
+}
+
 }  // namespace
 
 Mp4Track mp4_parse(const u8* data, size_t size) {
@@ -136,20 +167,41 @@ Mp4Track mp4_parse(const u8* data, size_t size) {
       c.need(8, "sample entry");
       u32 esz = c.u32v();
       u32 ety = c.u32v();
-      SCA_CHECK(ety == fourcc("avc1") || ety == fourcc("avc3"),
-                "mp4: video track is not AVC (avc1/avc3)");
+      const bool entry_jpeg = ety == fourcc("jpeg");
+      const bool entry_mp4v = ety == fourcc("mp4v");
+      SCA_CHECK(ety == fourcc("avc1") || ety == fourcc("avc3") ||
+                    entry_jpeg || entry_mp4v,
+                "mp4: video track is not AVC (avc1/avc3) or Motion-JPEG "
+                "(jpeg, or mp4v with objectTypeIndication 0x6C)");
       // VisualSampleEntry: 6 reserved + 2 data_ref_index + 16 predefined/
       // reserved + 2 width + 2 height + 4+4 dpi + 4 reserved + 2 frame_count
       // + 32 compressor + 2 depth + 2 predefined = 78 bytes
       c.skip(6 + 2 + 16, "sample entry fields");
-      c.u16v();  // coded width (SPS is authoritative)
-      c.u16v();  // coded height
+      u16 entry_w = c.u16v();  // coded width (for AVC the SPS is
+      u16 entry_h = c.u16v();  // authoritative)
       c.skip(4 + 4 + 4 + 2 + 32 + 2 + 2, "sample entry fields");
       // child boxes of the sample entry up to esz
       SCA_CHECK(esz >= 8 && entry_off + esz <= stsd->body_off + stsd->body_size,
                 "mp4: sample entry overrun");
       auto entry_kids =
           children(data, stsd->body_off + c.p, esz - (c.p - (entry_off - stsd->body_off)));
+      if (entry_jpeg || entry_mp4v) {
+        if (entry_mp4v) {
+          const Box* esds = find(entry_kids, fourcc("esds"));
+          SCA_CHECK(esds, "mp4: mp4v entry missing esds");
+          u32 oti = esds_object_type(data + esds->body_off, esds->body_size);
+          SCA_CHECK(oti == 0x6c,
+                    "mp4: mp4v track is not AVC or Motion-JPEG: its "
+                    "objectTypeIndication is 0x" +
+                        std::string(1, "0123456789abcdef"[(oti >> 4) & 15]) +
+                        std::string(1, "0123456789abcdef"[oti & 15]) +
+                        ", JPEG is 0x6c");
+        }
+        t.codec = "mjpeg";
+        t.width = entry_w;
+        t.height = entry_h;
+        t.length_size = 0;
+      } else {
       const Box* avcc = find(entry_kids, fourcc("avcC"));
       SCA_CHECK(avcc, "mp4: avc1 entry missing avcC");
       Cursor a{data + avcc->body_off, avcc->body_size};
@@ -176,6 +228,7 @@ Mp4Track mp4_parse(const u8* data, size_t size) {
       H264Sps s = h264_parse_sps(t.sps[0].data(), t.sps[0].size());
       t.width = s.width;
       t.height = s.height;
+      }
     }
 
     // ---- stts: total sample count + per-sample durations ----
@@ -329,7 +382,77 @@ struct W {
   }
 };
 
+// Everything of the file but the samples' content: `samples` are written
+// to one mdat chunk in order; `sample_entry` writes the stsd entry;
+// `keyframes` null means no stss box (every sample is a sync sample).
+std::vector<u8> write_file(
+    const std::vector<std::pair<const u8*, size_t>>& samples,
+    const std::vector<i64>* keyframes, const char* brand,
+    const std::function<void(W&)>& sample_entry, i32 width, i32 height,
+    double fps);
+
 }  // namespace
+
+std::vector<u8> mp4_write_mjpeg(const u8* stream, size_t stream_size,
+                                const std::vector<u64>& sample_offsets,
+                                const std::vector<u64>& sample_sizes,
+                                i32 width, i32 height, double fps) {
+  SCA_CHECK(!sample_offsets.empty() &&
+                sample_offsets.size() == sample_sizes.size(),
+            "mp4_write: empty or mismatched sample index");
+  SCA_CHECK(width >= 1 && width <= 65535 && height >= 1 && height <= 65535,
+            "mp4_write: frame size outside 1..65535");
+  std::vector<std::pair<const u8*, size_t>> samples;
+  u64 total = 0;
+  for (size_t s = 0; s < sample_offsets.size(); ++s) {
+    SCA_CHECK(sample_offsets[s] <= stream_size &&
+                  sample_sizes[s] <= stream_size - sample_offsets[s],
+              "mp4_write: sample range outside stream");
+    samples.emplace_back(stream + sample_offsets[s], (size_t)sample_sizes[s]);
+    total += sample_sizes[s];
+  }
+  SCA_CHECK(total < (1ull << 32) - (1u << 20),
+            "mp4_write: 4 GiB or more of samples need a 64-bit mdat");
+  auto entry = [&](W& f) {
+    size_t e = f.open("mp4v");
+    for (int i = 0; i < 6; ++i) f.u8v(0);  // reserved
+    f.u16v(1);                             // data ref index
+    f.u16v(0);
+    f.u16v(0);
+    for (int i = 0; i < 3; ++i) f.u32v(0);
+    f.u16v((u16)width);
+    f.u16v((u16)height);
+    f.u32v(0x00480000);  // 72 dpi
+    f.u32v(0x00480000);
+    f.u32v(0);
+    f.u16v(1);  // frame count
+    for (int i = 0; i < 32; ++i) f.u8v(0);  // compressor name
+    f.u16v(0x18);    // depth
+    f.u16v(0xffff);  // predefined
+    {
+      size_t at = f.open("esds");
+      f.u32v(0);     // version/flags
+      f.u8v(0x03);   // ES_Descriptor
+      f.u8v(3 + 2 + 13 + 2 + 1);  // its payload below
+      f.u16v(1);     // ES_ID
+      f.u8v(0);      // no dependence, URL or OCR; priority 0
+      f.u8v(0x04);   // DecoderConfigDescriptor
+      f.u8v(13);
+      f.u8v(0x6c);   // objectTypeIndication: Visual ISO/IEC 10918-1 (JPEG)
+      f.u8v(0x11);   // streamType 4 (visual) << 2 | upStream 0 | reserved 1
+      f.u8v(0);      // bufferSizeDB, 24 bits
+      f.u16v(0);
+      f.u32v(0);     // maxBitrate
+      f.u32v(0);     // avgBitrate
+      f.u8v(0x06);   // SLConfigDescriptor
+      f.u8v(1);
+      f.u8v(0x02);   // predefined: reserved for use in MP4 files
+      f.close(at);
+    }
+    f.close(e);
+  };
+  return write_file(samples, nullptr, "mp41", entry, width, height, fps);
+}
 
 std::vector<u8> mp4_write(const u8* stream, size_t stream_size,
                           const std::vector<u64>& sample_offsets,
@@ -343,9 +466,6 @@ std::vector<u8> mp4_write(const u8* stream, size_t stream_size,
             "mp4_write: empty or mismatched sample index");
   SCA_CHECK(!sps.empty() && !pps.empty(), "mp4_write: missing SPS/PPS");
   u32 n = (u32)sample_offsets.size();
-  u32 timescale = 90000;
-  u32 delta = (u32)(timescale / (fps > 0 ? fps : 30.0));
-  u64 duration = (u64)n * delta;
 
   // Convert each Annex-B access unit to AVCC (4-byte length prefixes),
   // stripping SPS/PPS/AUD NALs (they live in avcC).
@@ -381,6 +501,57 @@ std::vector<u8> mp4_write(const u8* stream, size_t stream_size,
     SCA_CHECK(!avcc[s].empty(), "mp4_write: sample has no slice NALs");
   }
 
+  std::vector<std::pair<const u8*, size_t>> samples;
+  for (u32 s = 0; s < n; ++s)
+    samples.emplace_back(avcc[s].data(), avcc[s].size());
+  auto entry = [&](W& f) {
+    size_t avc1 = f.open("avc1");
+    for (int i = 0; i < 6; ++i) f.u8v(0);  // reserved
+    f.u16v(1);                             // data ref index
+    f.u16v(0);
+    f.u16v(0);
+    for (int i = 0; i < 3; ++i) f.u32v(0);
+    f.u16v((u16)width);
+    f.u16v((u16)height);
+    f.u32v(0x00480000);  // 72 dpi
+    f.u32v(0x00480000);
+    f.u32v(0);
+    f.u16v(1);  // frame count
+    for (int i = 0; i < 32; ++i) f.u8v(0);  // compressor name
+    f.u16v(0x18);    // depth
+    f.u16v(0xffff);  // predefined
+    {
+      size_t avcc_at = f.open("avcC");
+      f.u8v(1);                      // configurationVersion
+      f.u8v(sps.size() > 1 ? sps[1] : 66);  // profile
+      f.u8v(sps.size() > 2 ? sps[2] : 0);   // compat
+      f.u8v(sps.size() > 3 ? sps[3] : 30);  // level
+      f.u8v(0xfc | 3);               // 4-byte lengths
+      f.u8v(0xe0 | 1);               // 1 SPS
+      f.u16v((u16)sps.size());
+      f.raw(sps.data(), sps.size());
+      f.u8v(1);                      // 1 PPS
+      f.u16v((u16)pps.size());
+      f.raw(pps.data(), pps.size());
+      f.close(avcc_at);
+    }
+    f.close(avc1);
+  };
+  return write_file(samples, &keyframe_indices, "avc1", entry, width, height,
+                    fps);
+}
+
+namespace {
+
+std::vector<u8> write_file(
+    const std::vector<std::pair<const u8*, size_t>>& samples,
+    const std::vector<i64>* keyframes, const char* brand,
+    const std::function<void(W&)>& sample_entry, i32 width, i32 height,
+    double fps) {
+  u32 n = (u32)samples.size();
+  u32 timescale = 90000;
+  u32 delta = (u32)(timescale / (fps > 0 ? fps : 30.0));
+  u64 duration = (u64)n * delta;
   W f;
   // ftyp
   {
@@ -388,7 +559,7 @@ std::vector<u8> mp4_write(const u8* stream, size_t stream_size,
     f.tag("isom");
     f.u32v(0x200);
     f.tag("isom");
-    f.tag("avc1");
+    f.tag(brand);
     f.close(at);
   }
   // mdat
@@ -397,7 +568,7 @@ std::vector<u8> mp4_write(const u8* stream, size_t stream_size,
     size_t at = f.open("mdat");
     for (u32 s = 0; s < n; ++s) {
       out_offsets[s] = f.b.size();
-      f.raw(avcc[s].data(), avcc[s].size());
+      f.raw(samples[s].first, samples[s].second);
     }
     f.close(at);
   }
@@ -489,37 +660,7 @@ std::vector<u8> mp4_write(const u8* stream, size_t stream_size,
     size_t stsd = f.open("stsd");
     f.u32v(0);
     f.u32v(1);
-    size_t avc1 = f.open("avc1");
-    for (int i = 0; i < 6; ++i) f.u8v(0);  // reserved
-    f.u16v(1);                             // data ref index
-    f.u16v(0);
-    f.u16v(0);
-    for (int i = 0; i < 3; ++i) f.u32v(0);
-    f.u16v((u16)width);
-    f.u16v((u16)height);
-    f.u32v(0x00480000);  // 72 dpi
-    f.u32v(0x00480000);
-    f.u32v(0);
-    f.u16v(1);  // frame count
-    for (int i = 0; i < 32; ++i) f.u8v(0);  // compressor name
-    f.u16v(0x18);    // depth
-    f.u16v(0xffff);  // predefined
-    {
-      size_t avcc_at = f.open("avcC");
-      f.u8v(1);                      // configurationVersion
-      f.u8v(sps.size() > 1 ? sps[1] : 66);  // profile
-      f.u8v(sps.size() > 2 ? sps[2] : 0);   // compat
-      f.u8v(sps.size() > 3 ? sps[3] : 30);  // level
-      f.u8v(0xfc | 3);               // 4-byte lengths
-      f.u8v(0xe0 | 1);               // 1 SPS
-      f.u16v((u16)sps.size());
-      f.raw(sps.data(), sps.size());
-      f.u8v(1);                      // 1 PPS
-      f.u16v((u16)pps.size());
-      f.raw(pps.data(), pps.size());
-      f.close(avcc_at);
-    }
-    f.close(avc1);
+    sample_entry(f);
     f.close(stsd);
   }
   {
@@ -530,11 +671,11 @@ std::vector<u8> mp4_write(const u8* stream, size_t stream_size,
     f.u32v(delta);
     f.close(at);
   }
-  {
+  if (keyframes) {
     size_t at = f.open("stss");
     f.u32v(0);
-    f.u32v((u32)keyframe_indices.size());
-    for (i64 k : keyframe_indices) f.u32v((u32)k + 1);
+    f.u32v((u32)keyframes->size());
+    for (i64 k : *keyframes) f.u32v((u32)k + 1);
     f.close(at);
   }
   {
@@ -551,7 +692,7 @@ std::vector<u8> mp4_write(const u8* stream, size_t stream_size,
     f.u32v(0);
     f.u32v(0);  // variable sizes
     f.u32v(n);
-    for (u32 s = 0; s < n; ++s) f.u32v((u32)avcc[s].size());
+    for (u32 s = 0; s < n; ++s) f.u32v((u32)samples[s].second);
     f.close(at);
   }
   {
@@ -568,5 +709,7 @@ std::vector<u8> mp4_write(const u8* stream, size_t stream_size,
   f.close(moov);
   return std::move(f.b);
 }
+
+}  // namespace
 
 }  // namespace sca

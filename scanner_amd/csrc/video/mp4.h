@@ -9,6 +9,13 @@
 // directly, giving per-sample absolute byte offsets + keyframes, and the
 // writer remuxes an indexed H.264 elementary stream back into a playable
 // .mp4 — no transcode, so no codec needed.
+//
+// Motion-JPEG tracks (video/mjpeg.h) are read and written too. Two sample
+// entries carry them: 'jpeg', QuickTime's Photo-JPEG, a plain
+// VisualSampleEntry; and 'mp4v' whose 'esds' DecoderConfigDescriptor has
+// objectTypeIndication 0x6C (ISO/IEC 14496-1: "Visual ISO/IEC 10918-1",
+// JPEG), which is what ffmpeg writes into .mp4. Each sample is one complete
+// JPEG file and every sample is a sync sample.
 #pragma once
 
 #include <string>
@@ -19,7 +26,9 @@
 namespace sca {
 
 struct Mp4Track {
-  i32 width = 0, height = 0;        // from the SPS (authoritative)
+  std::string codec = "h264";       // "h264" or "mjpeg"
+  i32 width = 0, height = 0;        // h264: from the SPS (authoritative);
+                                    // mjpeg: from the sample entry
   i32 length_size = 4;              // AVCC NAL length prefix bytes
   std::vector<std::vector<u8>> sps; // raw NAL bytes (no start code)
   std::vector<std::vector<u8>> pps;
@@ -30,8 +39,9 @@ struct Mp4Track {
   std::vector<u32> sample_deltas;   // per-sample duration (expanded stts)
 };
 
-// Parse the first AVC video track of an mp4 in memory. Throws ScannerError
-// on anything malformed or missing.
+// Parse the first video track of an mp4 or mov in memory: AVC, or
+// Motion-JPEG in one of the two sample entries above. Throws ScannerError on
+// anything malformed or missing.
 Mp4Track mp4_parse(const u8* data, size_t size);
 
 // Remux: wrap H.264 access units (Annex-B byte ranges of `stream` given by
@@ -44,5 +54,15 @@ std::vector<u8> mp4_write(const u8* stream, size_t stream_size,
                           const std::vector<u8>& sps,
                           const std::vector<u8>& pps, i32 width, i32 height,
                           double fps = 30.0);
+
+// Wrap Motion-JPEG samples (complete JPEG files, byte ranges of `stream`)
+// into an mp4: sample entry 'mp4v' with an 'esds' of ES_Descriptor ->
+// DecoderConfigDescriptor (objectTypeIndication 0x6C, streamType visual, no
+// DecoderSpecificInfo) -> SLConfigDescriptor (predefined 0x02); no 'stss',
+// so every sample is a sync sample.
+std::vector<u8> mp4_write_mjpeg(const u8* stream, size_t stream_size,
+                                const std::vector<u64>& sample_offsets,
+                                const std::vector<u64>& sample_sizes,
+                                i32 width, i32 height, double fps = 30.0);
 
 }  // namespace sca

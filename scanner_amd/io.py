@@ -40,8 +40,16 @@ class IOGenerator:
         # sink-side codec annotations (OpColumn.compress_video / lossless)
         compress = {c.name: c.op._compress[c.name].get("codec", "svc")
                     for c in cols if c.name in c.op._compress}
-        op = Op(self._client, "Output", cols,
-                args={"compress": compress} if compress else None,
-                output_columns=[])
+        # their options travel beside them, only for columns that have some
+        opts = {}
+        for c in cols:
+            kw = {k: v for k, v in c.op._compress.get(c.name, {}).items()
+                  if k != "codec"}
+            if kw:
+                opts[c.name] = kw
+        args = {"compress": compress} if compress else None
+        if opts:
+            args["compress_opts"] = opts
+        op = Op(self._client, "Output", cols, args=args, output_columns=[])
         op._streams = list(streams)
         return op

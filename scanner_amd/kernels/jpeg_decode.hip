@@ -170,6 +170,27 @@ thread_local double t_last_sync = 0;
 
 double jpeg_decode_gpu_last_sync_seconds() { return t_last_sync; }
 
+static_assert(kJpegDecLanes == kLanes, "one lane per restart segment");
+
+u32 jpeg_dec_colour_blocks(const JpegDecGeom& g) {
+  if (g.nc != 3) return 0;
+  u64 groups4 = ((u64)g.h * g.w + 3) / 4;
+  return (u32)((groups4 + kColourThreads - 1) / kColourThreads);
+}
+
+void jpeg_dec_enqueue(const JpegDecArgs& a, u32 ngroups, u32 colour_blocks,
+                      hipStream_t stream) {
+  if (ngroups) {
+    jpeg_entropy_idct_kernel<<<ngroups, kLanes, 0, stream>>>(a);
+    JPEG_DEC_CHECK(hipGetLastError());
+  }
+  if (colour_blocks && a.nfiles) {
+    jpeg_colour_kernel<<<dim3(colour_blocks, a.nfiles), kColourThreads, 0,
+                         stream>>>(a);
+    JPEG_DEC_CHECK(hipGetLastError());
+  }
+}
+
 void jpeg_decode_gpu(const std::vector<ImageBlob>& blobs,
                      const std::vector<JpegInfo>& infos, DeviceHandle dev,
                      void* stream, std::vector<DeviceFrame>& out_frames,

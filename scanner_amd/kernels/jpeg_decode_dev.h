@@ -45,6 +45,18 @@ struct JpegDecArgs {
   u32 nfiles;
 };
 
+// Launches of kernels/jpeg_decode.hip for a caller that has built the
+// records itself (kernels/mjpeg_index.hip, whose entropy bytes are a
+// device-resident span): the restart-segment kernel over `ngroups` group
+// records, then, when colour_blocks is not 0, the colour kernel over
+// a.nfiles files. Failures go to the status words, which the caller has set
+// to kJpegDecNoError.
+constexpr u32 kJpegDecLanes = 64;  // restart segments per workgroup
+void jpeg_dec_enqueue(const JpegDecArgs& a, u32 ngroups, u32 colour_blocks,
+                      hipStream_t stream);
+// x extent of the colour grid one file of this geometry needs (0: grey)
+u32 jpeg_dec_colour_blocks(const JpegDecGeom& g);
+
 // 8x8 samples of a grey file go straight to the image: only the part of the
 // block inside it
 __device__ inline void jpeg_store_block_grey(const u8 (&pix)[64], u8* img,

@@ -13,20 +13,53 @@ import msgpack
 from .common import ColumnType, DeviceType, FrameType, ScannerException
 
 
+# Sink codecs and the options each takes (the executor checks them again).
+SINK_CODEC_OPTIONS = {
+    "svc": (),
+    "mjpeg": ("quality", "subsampling"),
+}
+
+
+def check_sink_codec_options(codec, opts):
+    """Reject an unknown sink codec or an option it does not take, by name."""
+    if codec not in SINK_CODEC_OPTIONS:
+        raise ScannerException(
+            f"unknown sink codec '{codec}' (one of "
+            f"{sorted(SINK_CODEC_OPTIONS)})")
+    for k in opts:
+        if k not in SINK_CODEC_OPTIONS[codec]:
+            raise ScannerException(
+                f"unknown option '{k}' for sink codec '{codec}'")
+    if codec == "mjpeg":
+        q = opts.get("quality", 90)
+        if isinstance(q, bool) or not isinstance(q, int) or \
+                not 1 <= q <= 100:
+            raise ScannerException(
+                f"mjpeg quality must be an integer in 1..100, got {q!r}")
+        ss = opts.get("subsampling", "420")
+        if ss not in ("444", "420"):
+            raise ScannerException(
+                "mjpeg subsampling must be one of '444', '420', "
+                f"got {ss!r}")
+
+
 class OpColumn:
     def __init__(self, op, name, typ):
         self.op = op
         self.name = name
         self.type = typ
 
-    def compress(self, **kw):
+    def compress(self, codec="svc", **kw):
         """Mark a frame column for codec compression at the sink (parity:
-        OpColumn.compress_video op.py:47-106)."""
-        self.op._compress[self.name] = dict(kw)
+        OpColumn.compress_video op.py:47-106). codec 'svc' is lossless and
+        takes no options; 'mjpeg' takes quality (1..100, default 90) and
+        subsampling ('420', the default, or '444')."""
+        check_sink_codec_options(codec, kw)
+        self.op._compress[self.name] = dict(kw, codec=codec)
         return self
 
-    def compress_video(self, **kw):
-        return self.compress(codec="svc", **kw)
+    def compress_video(self, codec="svc", **kw):
+        return self.compress(codec=codec, **kw)
 
     def lossless(self):
         return self.compress(codec="svc")

@@ -53,12 +53,13 @@ class NamedStream:
 
 
 def ingest_videos(sc, entries, codec="svc", io_packet_size=128,
-                  inplace=False):
+                  inplace=False, **codec_options):
     """Batch-ingest videos; returns (streams, failures) where failures is
     a list of (name, error) for inputs that could not be ingested (parity:
     Client.ingest_videos + FailedVideo reporting, ingest.cpp:867).
 
-    entries: list of (name, frames-or-npy-path).
+    entries: list of (name, frames-or-npy-path). codec_options (quality,
+    subsampling) go to codec='mjpeg'.
     """
     streams, failures = [], []
     for name, src in entries:
@@ -66,11 +67,13 @@ def ingest_videos(sc, entries, codec="svc", io_packet_size=128,
             if isinstance(src, str):
                 streams.append(NamedVideoStream(sc, name, path=src,
                                                 codec=codec,
-                                                io_packet_size=io_packet_size))
+                                                io_packet_size=io_packet_size,
+                                                **codec_options))
             else:
                 streams.append(NamedVideoStream(sc, name, frames=src,
                                                 codec=codec,
-                                                io_packet_size=io_packet_size))
+                                                io_packet_size=io_packet_size,
+                                                **codec_options))
         except Exception as e:
             failures.append((name, f"{type(e).__name__}: {e}"))
     return streams, failures
@@ -80,13 +83,27 @@ class NamedVideoStream(NamedStream):
     """A frame column stored as a (possibly codec-compressed) video table
     (parity: NamedVideoStream storage.py:250-374). With no codec libraries
     in this environment, ingest takes raw frames (numpy [N,H,W,C] u8) or an
-    .npy path and stores them raw or SVC-compressed."""
+    .npy path and stores them raw, SVC-compressed or, with codec='mjpeg',
+    as Motion-JPEG (quality 1..100, default 90; subsampling '420', the
+    default, or '444'). A .mp4 or .mov path with an H.264 or a Motion-JPEG
+    track is stored as it is."""
 
     def __init__(self, sc, name, path=None, frames=None, codec="svc",
-                 column=None, io_packet_size=128):
+                 column=None, io_packet_size=128, quality=None,
+                 subsampling=None):
         super().__init__(sc, name, column)
+        if codec != "mjpeg":
+            for k, v in (("quality", quality), ("subsampling", subsampling)):
+                if v is not None:
+                    raise ScannerException(
+                        f"unknown option '{k}' for codec '{codec}'")
+        self._codec_options = {}
+        if quality is not None:
+            self._codec_options["quality"] = quality
+        if subsampling is not None:
+            self._codec_options["subsampling"] = subsampling
         if path is not None and not self.committed() and \
-                path.lower().endswith((".mp4", ".h264", ".264")):
+                path.lower().endswith((".mp4", ".mov", ".h264", ".264")):
             # real video file: demux + H.264 keyframe index (pure parsing;
             # parity: ingest.cpp:175-380). Decode of the result needs the
             # rocDecode/VCN hardware decoder.
@@ -118,7 +135,8 @@ class NamedVideoStream(NamedStream):
         if frames.ndim != 4:
             raise ScannerException("frames must be [N,H,W,C] u8")
         _core.write_video_table(self._sc._db, self.name, self._column or
-                                "frame", frames, io_packet_size, codec)
+                                "frame", frames, io_packet_size, codec,
+                                **self._codec_options)
 
     def load(self, fn=None, rows=None):
         from . import _core
@@ -144,10 +162,11 @@ class NamedVideoStream(NamedStream):
         return path
 
     def save_mp4(self, path, fps=30.0):
-        """Remux an ingested H.264 table back into a playable .mp4
+        """Remux an H.264 or a Motion-JPEG table into a playable .mp4
         (no transcode, so no codec library needed; parity:
-        NamedVideoStream.save_mp4, storage.py:353-374). Only valid for
-        tables ingested from real video (codec 'h264')."""
+        NamedVideoStream.save_mp4, storage.py:353-374). Valid for tables
+        ingested from real video (codec 'h264') and for mjpeg tables,
+        ingested or computed (compress_video(codec='mjpeg'))."""
         from . import _core
         _core.export_mp4(self._sc._db, self.name, self.column_name(),
                          path, fps)

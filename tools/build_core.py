@@ -38,6 +38,7 @@ CPP_SOURCES = [
     "csrc/engine/executor.cpp",
     "csrc/video/svc_cpu.cpp",
     "csrc/video/span_cache.cpp",
+    "csrc/video/mjpeg.cpp",
     "csrc/video/h264.cpp",
     "csrc/video/mp4.cpp",
     "csrc/video/ingest.cpp",
@@ -52,6 +53,7 @@ HIP_SOURCES = [
     "kernels/png_encode.hip",
     "kernels/jpeg_decode.hip",
     "kernels/jpeg_sync_decode.hip",
+    "kernels/mjpeg_index.hip",
     "kernels/color.hip",
     "kernels/optflow.hip",
     "kernels/gemm_mfma.hip",

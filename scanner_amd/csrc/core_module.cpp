@@ -22,6 +22,7 @@
 #include "video/mp4.h"
 #include "ops/dnn_model.h"
 #include "ops/image_decode.h"
+#include "ops/jpeg_progressive_common.h"
 #include "ops/jpeg_common.h"
 #include "ops/jpeg_sync_common.h"
 #include "ops/kernel.h"
@@ -1267,9 +1268,12 @@ PYBIND11_MODULE(_core, m) {
     std::memcpy(a.mutable_data(), img.pixels.data(), img.pixels.size());
     return a;
   };
-  m.def("jpeg_decode_info", [](py::bytes blob) {
+  m.def("jpeg_decode_info", [](py::bytes blob, const std::string& progressive) {
+    JpegParseOptions po;
+    po.allow_progressive =
+        jpeg_progressive_option(progressive, "jpeg_decode_info");
     std::string s = blob;
-    JpegInfo in = jpeg_parse((const u8*)s.data(), s.size());
+    JpegInfo in = jpeg_parse((const u8*)s.data(), s.size(), po);
     py::dict d;
     d["h"] = in.g.h;
     d["w"] = in.g.w;
@@ -1283,21 +1287,80 @@ PYBIND11_MODULE(_core, m) {
       segs.append(py::make_tuple(sg.begin, sg.end, sg.first_mcu,
                                  sg.mcu_count));
     d["segments"] = segs;
+    d["progressive"] = in.progressive;
+    py::list scans;
+    for (auto& sc : in.scans) {
+      py::dict e;
+      py::list comps;
+      for (u32 c = 0; c < sc.ncomp; ++c) comps.append(sc.comp[c]);
+      e["components"] = comps;
+      e["ss"] = sc.ss;
+      e["se"] = sc.se;
+      e["ah"] = sc.ah;
+      e["al"] = sc.al;
+      e["restart_interval"] = sc.restart_interval;
+      e["units"] = sc.units;
+      e["segment_count"] = sc.segments.size();
+      py::list ssegs;
+      for (auto& sg : sc.segments)
+        ssegs.append(py::make_tuple(sg.begin, sg.end, sg.first_mcu,
+                                    sg.mcu_count));
+      e["segments"] = ssegs;
+      scans.append(e);
+    }
+    d["scans"] = scans;
     return d;
-  });
+  }, py::arg("blob"), py::arg("progressive") = "reject");
   // the oracle: file bytes -> [H,W,C] u8
-  m.def("jpeg_cpu_decode", [image_to_array](py::bytes blob) {
+  m.def("jpeg_cpu_decode", [image_to_array](py::bytes blob,
+                                            const std::string& progressive) {
+    JpegParseOptions po;
+    po.allow_progressive =
+        jpeg_progressive_option(progressive, "jpeg_cpu_decode");
     std::string s = blob;
-    return image_to_array(jpeg_decode_cpu((const u8*)s.data(), s.size()));
-  });
+    return image_to_array(jpeg_decode_cpu((const u8*)s.data(), s.size(), po));
+  }, py::arg("blob"), py::arg("progressive") = "reject");
+  // debug seam: the quantised coefficients of a baseline or progressive
+  // file, per component as int16 [blocks_y, blocks_x, 64] in natural order
+  // over the component's own raster, ceil(comp_w / 8) x ceil(comp_h / 8)
+  m.def("jpeg_decode_coefficients", [](py::bytes blob,
+                                       const std::string& progressive) {
+    JpegParseOptions po;
+    po.allow_progressive =
+        jpeg_progressive_option(progressive, "jpeg_decode_coefficients");
+    std::string s = blob;
+    JpegInfo in = jpeg_parse((const u8*)s.data(), s.size(), po);
+    std::vector<i16> coef;
+    jpeg_coefficients_cpu((const u8*)s.data(), in, coef);
+    py::list res;
+    for (u32 c = 0; c < (u32)in.g.nc; ++c) {
+      u32 bw, bh;
+      jpeg_prog_comp_blocks(in.g, c, bw, bh);
+      py::array_t<i16> a({(i64)bh, (i64)bw, (i64)64});
+      i16* dst = a.mutable_data();
+      for (u32 by = 0; by < bh; ++by)
+        for (u32 bx = 0; bx < bw; ++bx)
+          std::memcpy(dst + ((size_t)by * bw + bx) * 64,
+                      coef.data() +
+                          (size_t)jpeg_prog_block_index(in.g, c, bx, by) * 64,
+                      128);
+      res.append(a);
+    }
+    return res;
+  }, py::arg("blob"), py::arg("progressive") = "reject");
   m.def("png_cpu_decode", [image_to_array](py::bytes blob) {
     std::string s = blob;
     return image_to_array(png_decode((const u8*)s.data(), s.size()));
   });
-  m.def("image_cpu_decode", [image_to_array](py::bytes blob) {
+  m.def("image_cpu_decode", [image_to_array](py::bytes blob,
+                                             const std::string& progressive) {
+    JpegParseOptions po;
+    po.allow_progressive =
+        jpeg_progressive_option(progressive, "image_cpu_decode");
     std::string s = blob;
-    return image_to_array(image_decode_cpu((const u8*)s.data(), s.size()));
-  });
+    return image_to_array(
+        image_decode_cpu((const u8*)s.data(), s.size(), po));
+  }, py::arg("blob"), py::arg("progressive") = "reject");
   // dequantised int32 blocks [N,64] (natural order; values are clamped to
   // the decoder's coefficient limit) -> u8 samples [N,64]
   m.def("jpeg_idct_blocks",
@@ -1352,16 +1415,22 @@ PYBIND11_MODULE(_core, m) {
   // order; with host_rows=True also the number of rows the CPU decoders
   // handled (PNG; JPEG without DRI unless serial_scan="device", and then
   // those that failed verification); with stats=True also a dict of the
-  // self-synchronising decoder's row counts.
+  // self-synchronising decoder's row counts. progressive="decode" allows
+  // progressive files (image_decode.h says which go to the device) and adds
+  // their device row count to that dict.
   m.def("jpeg_gpu_decode",
         [](const std::vector<py::bytes>& blobs, bool want_host_rows,
-           const std::string& serial_scan, u32 chunk_bytes, bool want_stats)
-            -> py::object {
+           const std::string& serial_scan, u32 chunk_bytes, bool want_stats,
+           const std::string& progressive) -> py::object {
+          JpegParseOptions po;
+          po.allow_progressive =
+              jpeg_progressive_option(progressive, "jpeg_gpu_decode");
           SCA_CHECK(have_gpu(), "jpeg_gpu_decode needs a GPU");
           SCA_CHECK(serial_scan == "host" || serial_scan == "device",
                     "serial_scan must be 'host' or 'device', got '" +
                         serial_scan + "'");
           JpegGpuOptions opt;
+          opt.progressive = po.allow_progressive;
           opt.serial_scan_on_device = serial_scan == "device";
           opt.chunk_bytes = chunk_bytes;
           DeviceHandle dev{DeviceType::GPU, 0};
@@ -1372,7 +1441,7 @@ PYBIND11_MODULE(_core, m) {
             ib.push_back({(const u8*)data[i].data(), data[i].size()});
             if (is_jpeg(ib[i].data, ib[i].size)) {
               try {
-                infos[i] = jpeg_parse(ib[i].data, ib[i].size);
+                infos[i] = jpeg_parse(ib[i].data, ib[i].size, po);
               } catch (const ScannerError& err) {
                 throw ScannerError("ImageDecoder: row " + std::to_string(i) +
                                    " of the batch: " + err.what());
@@ -1400,6 +1469,9 @@ PYBIND11_MODULE(_core, m) {
           py::dict sd;
           sd["sync_rows"] = gs.sync_rows;
           sd["fallback_rows"] = gs.fallback_rows;
+          // only on request: the dict of a default call is what it was
+          if (po.allow_progressive)
+            sd["progressive_rows"] = gs.progressive_rows;
           if (want_host_rows && want_stats)
             return py::make_tuple(res, host_rows, sd);
           if (want_host_rows) return py::make_tuple(res, host_rows);
@@ -1408,7 +1480,7 @@ PYBIND11_MODULE(_core, m) {
         },
         py::arg("blobs"), py::arg("host_rows") = false,
         py::arg("serial_scan") = "host", py::arg("chunk_bytes") = 0,
-        py::arg("stats") = false);
+        py::arg("stats") = false, py::arg("progressive") = "reject");
   // Seconds of each of `iters` decodes of the batch, every one ending with
   // the frames resident in HBM. mode "gpu": jpeg_parse + jpeg_decode_gpu
   // (compressed H2D inside; serial_scan and chunk_bytes as for
@@ -1418,7 +1490,10 @@ PYBIND11_MODULE(_core, m) {
   m.def("jpeg_decode_bench",
         [](const std::vector<py::bytes>& blobs, i32 iters,
            const std::string& mode, const std::string& serial_scan,
-           u32 chunk_bytes) {
+           u32 chunk_bytes, const std::string& progressive) {
+          JpegParseOptions po;
+          po.allow_progressive =
+              jpeg_progressive_option(progressive, "jpeg_decode_bench");
           SCA_CHECK(have_gpu(), "jpeg_decode_bench needs a GPU");
           SCA_CHECK(serial_scan == "host" || serial_scan == "device",
                     "serial_scan must be 'host' or 'device', got '" +
@@ -1426,6 +1501,7 @@ PYBIND11_MODULE(_core, m) {
           JpegGpuOptions opt;
           opt.serial_scan_on_device = serial_scan == "device";
           opt.chunk_bytes = chunk_bytes;
+          opt.progressive = po.allow_progressive;
           SCA_CHECK(mode == "gpu" || mode == "cpu" || mode == "upload",
                     "mode must be 'gpu', 'cpu' or 'upload'");
           SCA_CHECK(!blobs.empty() && iters > 0, "empty benchmark");
@@ -1440,7 +1516,7 @@ PYBIND11_MODULE(_core, m) {
               std::vector<JpegInfo> infos(data.size());
               for (size_t i = 0; i < data.size(); ++i) {
                 ib.push_back({(const u8*)data[i].data(), data[i].size()});
-                infos[i] = jpeg_parse(ib[i].data, ib[i].size);
+                infos[i] = jpeg_parse(ib[i].data, ib[i].size, po);
               }
               std::vector<DeviceFrame> frames;
               jpeg_decode_gpu(ib, infos, dev, per_thread_hip_stream(),
@@ -1458,7 +1534,7 @@ PYBIND11_MODULE(_core, m) {
                   imgs.back().pixels.assign(d.begin(), d.end());
                 } else {
                   imgs.push_back(
-                      jpeg_decode_cpu((const u8*)d.data(), d.size()));
+                      jpeg_decode_cpu((const u8*)d.data(), d.size(), po));
                 }
                 total += (imgs.back().pixels.size() + 255) / 256 * 256;
               }
@@ -1483,7 +1559,8 @@ PYBIND11_MODULE(_core, m) {
           return secs;
         },
         py::arg("blobs"), py::arg("iters") = 1, py::arg("mode") = "gpu",
-        py::arg("serial_scan") = "host", py::arg("chunk_bytes") = 0);
+        py::arg("serial_scan") = "host", py::arg("chunk_bytes") = 0,
+        py::arg("progressive") = "reject");
   // seconds the calling thread's last jpeg_decode_gpu waited in its stream
   // synchronise (the rest of the call is host work: parse, pack, enqueue)
   m.def("jpeg_decode_last_sync_seconds", &jpeg_decode_gpu_last_sync_seconds);

@@ -21,6 +21,7 @@ class ImageDecoderKernelCPU : public BatchedKernel {
     // where a GPU kernel decodes scans without restart markers; nothing to
     // choose here, but a graph may carry the argument on either device
     image_decoder_serial_scan_on_device(cfg.args);
+    parse_.allow_progressive = image_decoder_progressive(cfg.args);
   }
   void execute_batch(const BatchedElements& in, BatchedElements& out) override {
     for (size_t i = 0; i < in[0].size(); ++i) {
@@ -34,7 +35,7 @@ class ImageDecoderKernelCPU : public BatchedKernel {
       SCA_CHECK(!b.is_frame, "ImageDecoder needs a bytes input");
       DecodedImage img;
       try {
-        img = image_decode_cpu(b.buffer, b.size);
+        img = image_decode_cpu(b.buffer, b.size, parse_);
       } catch (const ScannerError& err) {
         throw ScannerError("ImageDecoder: row " + std::to_string(i) +
                            " of the batch: " + err.what());
@@ -51,6 +52,9 @@ class ImageDecoderKernelCPU : public BatchedKernel {
       out[0].push_back(e);
     }
   }
+
+ private:
+  JpegParseOptions parse_;
 };
 
 }  // namespace
@@ -60,6 +64,11 @@ bool image_decoder_serial_scan_on_device(const std::vector<u8>& args) {
   SCA_CHECK(v == "host" || v == "device",
             "ImageDecoder supports serial_scan=host|device, got '" + v + "'");
   return v == "device";
+}
+
+bool image_decoder_progressive(const std::vector<u8>& args) {
+  return jpeg_progressive_option(
+      mp::decode(args).get_str("progressive", "reject"), "ImageDecoder");
 }
 
 void register_image_decoder_op() {

@@ -10,7 +10,8 @@
 // caller asks for the self-synchronising decoder of
 // kernels/jpeg_sync_decode.hip, which this file's host side feeds from the
 // same staging buffer and whose rows share the colour kernel and the status
-// words (records of both: kernels/jpeg_decode_dev.h).
+// words (records of both: kernels/jpeg_decode_dev.h). Progressive files go
+// the same way to kernels/jpeg_progressive_decode.hip.
 //
 // Per batch (any mix of shapes, samplings and tables):
 //   host     parse every file; pack status words, one descriptor per file
@@ -211,26 +212,47 @@ void jpeg_decode_gpu(const std::vector<ImageBlob>& blobs,
   hipStream_t s = (hipStream_t)stream;
 
   // ---- classify, decode the host rows, lay out the outputs ----
-  // 0 null, 1 device by restart segments, 2 host, 3 device by chunks
+  // 0 null, 1 device by restart segments, 2 host, 3 device by chunks,
+  // 4 device, progressive
   std::vector<int> kind(n, 0);
-  auto on_device = [&](size_t i) { return kind[i] == 1 || kind[i] == 3; };
+  auto on_device = [&](size_t i) {
+    return kind[i] == 1 || kind[i] == 3 || kind[i] == 4;
+  };
   std::vector<DecodedImage> host_img(n);
   std::vector<u64> out_off(n, 0);
   u64 out_total = 0, host_pix_total = 0;
   i32 live = 0;
-  size_t ndev = 0, nsync = 0;
+  size_t ndev = 0, nsync = 0, nprog = 0;
   for (size_t i = 0; i < n; ++i) {
     if (!blobs[i].data) continue;
     DeviceFrame& fr = out_frames[i];
     bool jpeg = is_jpeg(blobs[i].data, blobs[i].size);
+    bool prog = jpeg && infos[i].progressive;
+    bool prog_dev = false;
+    if (prog) {
+      SCA_CHECK(opt.progressive,
+                "ImageDecoder: row " + std::to_string(i) + " of the batch: "
+                "progressive JPEG (SOF2) is not supported");
+      // a scan without a restart interval is one lane of the scan kernel:
+      // on the device only where the caller asked for serial scans there
+      bool all_dri = true;
+      for (const JpegScan& sc : infos[i].scans)
+        all_dri = all_dri && sc.restart_interval != 0;
+      prog_dev = (all_dri || opt.serial_scan_on_device) &&
+                 !infos[i].scans.empty() &&
+                 infos[i].scans.size() <= kJpegProgMaxDeviceScans;
+    }
     bool by_chunks =
-        jpeg && opt.serial_scan_on_device && infos[i].restart_interval == 0 &&
+        jpeg && !prog && opt.serial_scan_on_device &&
+        infos[i].restart_interval == 0 &&
         infos[i].segments.size() == 1 &&
         infos[i].segments[0].end - infos[i].segments[0].begin <
             kJpegSyncMaxScanBytes;
-    if ((jpeg && infos[i].restart_interval != 0) || by_chunks) {
-      kind[i] = by_chunks ? 3 : 1;
+    if ((jpeg && !prog && infos[i].restart_interval != 0) || by_chunks ||
+        prog_dev) {
+      kind[i] = prog_dev ? 4 : by_chunks ? 3 : 1;
       nsync += by_chunks;
+      nprog += prog_dev;
       ++ndev;
       fr.h = infos[i].g.h;
       fr.w = infos[i].g.w;
@@ -268,11 +290,28 @@ void jpeg_decode_gpu(const std::vector<ImageBlob>& blobs,
   // ---- staging layout: status | files | groups | segments | chunked
   // files | their groups | entropy | (host only) pixels of the host rows ----
   size_t ngroups = 0, nsegs = 0, nsgroups = 0, nchunks = 0;
-  u64 entropy_total = 0, planes_total = 0, coef_total = 0;
+  size_t npdescs = 0, npgroups = 0, npsegs = 0, nlaunch = 0;
+  u64 entropy_total = 0, planes_total = 0, coef_total = 0, pcoef_total = 0;
+  // [first, last) entropy-coded byte of a device row
+  auto entropy_range = [&](size_t i, u32& base, u32& len) {
+    const JpegInfo& in = infos[i];
+    const auto& first = in.progressive ? in.scans.front().segments : in.segments;
+    const auto& last = in.progressive ? in.scans.back().segments : in.segments;
+    base = first.front().begin;
+    len = last.back().end - base;
+  };
   for (size_t i = 0; i < n; ++i) {
     if (!on_device(i)) continue;
     const JpegInfo& in = infos[i];
-    if (kind[i] == 3) {
+    if (kind[i] == 4) {
+      npdescs += in.scans.size();
+      nlaunch = std::max(nlaunch, in.scans.size());
+      for (const JpegScan& sc : in.scans) {
+        npsegs += sc.segments.size();
+        npgroups += (sc.segments.size() + kLanes - 1) / kLanes;
+      }
+      pcoef_total += (u64)in.g.nmcu * in.g.blocks_per_mcu * 64;
+    } else if (kind[i] == 3) {
       u32 nc = jpeg_sync_chunk_count(
           in.segments[0].end - in.segments[0].begin, chunk_bytes);
       nchunks += nc;
@@ -282,20 +321,27 @@ void jpeg_decode_gpu(const std::vector<ImageBlob>& blobs,
       nsegs += in.segments.size();
       ngroups += (in.segments.size() + kLanes - 1) / kLanes;
     }
-    entropy_total +=
-        align_up(in.segments.back().end - in.segments.front().begin, 16);
+    u32 ebase, elen;
+    entropy_range(i, ebase, elen);
+    entropy_total += align_up(elen, 16);
     if (in.g.nc == 3)
       planes_total += align_up((u64)in.g.y_stride * in.g.y_rows, 256) +
                       2 * align_up((u64)in.g.c_stride * in.g.c_rows, 256);
   }
   u64 status_off = 0;
-  u64 files_off = align_up(status_off + 4 * ndev, 256);
+  // the second ndev words: the failing scan of a progressive row
+  u64 files_off = align_up(status_off + 8 * ndev, 256);
   u64 groups_off = align_up(files_off + sizeof(JpegDecFile) * ndev, 256);
   u64 segs_off = align_up(groups_off + sizeof(JpegDecGroup) * ngroups, 256);
   u64 sfiles_off = align_up(segs_off + sizeof(JpegDecSeg) * nsegs, 256);
   u64 sgroups_off = align_up(sfiles_off + sizeof(JpegSyncFile) * nsync, 256);
-  u64 entropy_off =
+  u64 pdescs_off =
       align_up(sgroups_off + sizeof(JpegSyncGroup) * nsgroups, 256);
+  u64 pgroups_off =
+      align_up(pdescs_off + sizeof(JpegProgScanDesc) * npdescs, 256);
+  u64 psegs_off = align_up(pgroups_off + sizeof(JpegProgGroup) * npgroups, 256);
+  u64 pfiles_off = align_up(psegs_off + sizeof(JpegDecSeg) * npsegs, 256);
+  u64 entropy_off = align_up(pfiles_off + sizeof(JpegProgFile) * nprog, 256);
   u64 upload = align_up(entropy_off + entropy_total, 256);
   // device only, behind the upload: planes | chunk records | first blocks |
   // group exits | coefficients
@@ -304,10 +350,11 @@ void jpeg_decode_gpu(const std::vector<ImageBlob>& blobs,
   u64 gexit_off = align_up(first_off + 4 * nchunks, 256);
   u64 coef_off =
       align_up(gexit_off + 2 * sizeof(JpegSyncState) * nsgroups, 256);
-  u64 ws_size = coef_off + coef_total * sizeof(i16);
+  u64 pcoef_off = align_up(coef_off + coef_total * sizeof(i16), 256);
+  u64 ws_size = pcoef_off + pcoef_total * sizeof(i16);
   u64 host_pix_off = upload;
   u64 status_back_off = host_pix_off + host_pix_total;
-  u64 staging_size = status_back_off + align_up(4 * ndev, 256) + 256;
+  u64 staging_size = status_back_off + align_up(8 * ndev, 256) + 256;
   SCA_CHECK(upload < (1ull << 32), "jpeg decode: batch of 4 GiB or more");
 
   u8* out_block = nullptr;
@@ -341,13 +388,26 @@ void jpeg_decode_gpu(const std::vector<ImageBlob>& blobs,
       u8* entropy = staging + entropy_off;
       auto* sfiles = reinterpret_cast<JpegSyncFile*>(staging + sfiles_off);
       auto* sgroups = reinterpret_cast<JpegSyncGroup*>(staging + sgroups_off);
+      auto* pdescs = reinterpret_cast<JpegProgScanDesc*>(staging + pdescs_off);
+      auto* pgroups = reinterpret_cast<JpegProgGroup*>(staging + pgroups_off);
+      auto* psegs = reinterpret_cast<JpegDecSeg*>(staging + psegs_off);
+      auto* pfiles = reinterpret_cast<JpegProgFile*>(staging + pfiles_off);
       u32 fi = 0, gi = 0, si = 0, sfi = 0, sgi = 0, ci = 0;
-      u32 max_rounds = 0, max_nblk = 0;
-      u64 epos = 0, ppos = 0, cpos = 0;
+      u32 pdi = 0, psi = 0, pfi = 0;
+      u32 max_rounds = 0, max_nblk = 0, max_pnblk = 0;
+      u64 epos = 0, ppos = 0, cpos = 0, pcpos = 0;
+      // progressive group records are ordered by scan index, then file:
+      // one launch per scan index over a contiguous range
+      struct PendingGroup {
+        u32 scan;
+        JpegProgGroup g;
+      };
+      std::vector<PendingGroup> pending;
       for (size_t i = 0; i < n; ++i) {
         if (!on_device(i)) continue;
         const JpegInfo& in = infos[i];
         status[fi] = kNoError;
+        status[ndev + fi] = kNoError;
         JpegDecFile& f = files[fi];
         std::memset(&f, 0, sizeof(f));
         f.g = in.g;
@@ -371,10 +431,46 @@ void jpeg_decode_gpu(const std::vector<ImageBlob>& blobs,
           f.dc[c] = in.dc[c];
           f.ac[c] = in.ac[c];
         }
-        u32 base = in.segments.front().begin;
-        u32 len = in.segments.back().end - base;
+        u32 base, len;
+        entropy_range(i, base, len);
         std::memcpy(entropy + epos, blobs[i].data + base, len);
-        if (kind[i] == 3) {
+        if (kind[i] == 4) {
+          JpegProgFile& pf = pfiles[pfi++];
+          pf.file = fi;
+          pf.nblk = in.g.nmcu * in.g.blocks_per_mcu;
+          pf.coef_off = pcpos;
+          max_pnblk = std::max(max_pnblk, pf.nblk);
+          for (size_t k = 0; k < in.scans.size(); ++k) {
+            const JpegScan& sc = in.scans[k];
+            JpegProgScanDesc& d = pdescs[pdi];
+            std::memset(&d, 0, sizeof(d));
+            d.g = in.g;
+            d.file = fi;
+            d.ncomp = sc.ncomp;
+            d.comp = sc.comp[0];
+            d.ss = sc.ss;
+            d.se = sc.se;
+            d.ah = sc.ah;
+            d.al = sc.al;
+            d.coef_off = pcpos;
+            std::memcpy(d.zz2nat, in.zz2nat, sizeof(d.zz2nat));
+            if (sc.ss == 0) {
+              for (int c = 0; c < 3; ++c) d.tab[c] = sc.dc[c];
+            } else {
+              d.tab[0] = sc.ac[sc.comp[0]];
+            }
+            u32 nseg = (u32)sc.segments.size();
+            for (u32 j = 0; j < nseg; j += kLanes)
+              pending.push_back(
+                  {(u32)k, {pdi, psi + j, std::min(kLanes, nseg - j), j}});
+            for (const JpegSegment& sg : sc.segments)
+              psegs[psi++] = {(u32)(epos + sg.begin - base),
+                              (u32)(epos + sg.end - base), sg.first_mcu,
+                              sg.mcu_count};
+            ++pdi;
+          }
+          pcpos += (u64)pf.nblk * 64;
+        } else if (kind[i] == 3) {
           JpegSyncFile& sf = sfiles[sfi];
           std::memset(&sf, 0, sizeof(sf));
           sf.file = fi;
@@ -406,6 +502,19 @@ void jpeg_decode_gpu(const std::vector<ImageBlob>& blobs,
         epos += align_up(len, 16);
         ++fi;
       }
+      std::vector<u32> launch_group0(nlaunch + 1, 0);
+      if (nprog) {
+        std::stable_sort(pending.begin(), pending.end(),
+                         [](const PendingGroup& x, const PendingGroup& y) {
+                           return x.scan < y.scan;
+                         });
+        for (size_t j = 0; j < pending.size(); ++j) {
+          pgroups[j] = pending[j].g;
+          ++launch_group0[pending[j].scan + 1];
+        }
+        for (size_t k = 0; k < nlaunch; ++k)
+          launch_group0[k + 1] += launch_group0[k];
+      }
       JPEG_DEC_CHECK(
           hipMemcpyAsync(ws, staging, upload, hipMemcpyHostToDevice, s));
       JpegDecArgs a{};
@@ -436,13 +545,27 @@ void jpeg_decode_gpu(const std::vector<ImageBlob>& blobs,
         sa.max_nblk = max_nblk;
         jpeg_sync_enqueue(sa, s);
       }
+      if (nprog) {
+        JpegProgArgs pa{};
+        pa.dec = a;
+        pa.descs = reinterpret_cast<const JpegProgScanDesc*>(ws + pdescs_off);
+        pa.groups = reinterpret_cast<const JpegProgGroup*>(ws + pgroups_off);
+        pa.segs = reinterpret_cast<const JpegDecSeg*>(ws + psegs_off);
+        pa.pfiles = reinterpret_cast<const JpegProgFile*>(ws + pfiles_off);
+        pa.fail_scan = a.status + ndev;
+        pa.coef = reinterpret_cast<i16*>(ws + pcoef_off);
+        pa.coef_count = pcoef_total;
+        pa.npfiles = (u32)nprog;
+        pa.max_nblk = max_pnblk;
+        jpeg_prog_enqueue(pa, launch_group0.data(), (u32)nlaunch, s);
+      }
       if (max_colour_blocks) {
         jpeg_colour_kernel<<<dim3(max_colour_blocks, (u32)ndev),
                              kColourThreads, 0, s>>>(a);
         JPEG_DEC_CHECK(hipGetLastError());
       }
       JPEG_DEC_CHECK(hipMemcpyAsync(staging + status_back_off,
-                                    ws + status_off, 4 * ndev,
+                                    ws + status_off, 8 * ndev,
                                     hipMemcpyDeviceToHost, s));
     }
     // host rows: pixels through the pinned staging
@@ -468,8 +591,15 @@ void jpeg_decode_gpu(const std::vector<ImageBlob>& blobs,
       u64 fallback_total = 0;
       for (size_t i = 0; i < n; ++i) {
         if (!on_device(i)) continue;
-        u32 st = back[fi++];
+        u32 st = back[fi];
+        u32 failed_scan = back[ndev + fi];
+        ++fi;
         if (st == kNoError) continue;
+        if (kind[i] == 4)
+          throw ScannerError("ImageDecoder: row " + std::to_string(i) +
+                             " of the batch: check failed: " +
+                             jpeg_entropy_error(st & 15u, st >> 4,
+                                                failed_scan));
         if (kind[i] == 1)
           throw ScannerError("ImageDecoder: row " + std::to_string(i) +
                              " of the batch: check failed: " +
@@ -503,6 +633,7 @@ void jpeg_decode_gpu(const std::vector<ImageBlob>& blobs,
       if (stats) {
         stats->fallback_rows = (i64)fell_back.size();
         stats->sync_rows = (i64)nsync - stats->fallback_rows;
+        stats->progressive_rows = (i64)nprog;
       }
     }
   } catch (...) {
@@ -523,6 +654,8 @@ class ImageDecoderKernelGPU : public BatchedKernel {
   explicit ImageDecoderKernelGPU(const KernelConfig& cfg)
       : BatchedKernel(cfg) {
     opt_.serial_scan_on_device = image_decoder_serial_scan_on_device(cfg.args);
+    opt_.progressive = image_decoder_progressive(cfg.args);
+    parse_.allow_progressive = opt_.progressive;
   }
 
   void execute_batch(const BatchedElements& in, BatchedElements& out) override {
@@ -553,7 +686,7 @@ class ImageDecoderKernelGPU : public BatchedKernel {
         ++live;
         if (is_jpeg(p, b.size)) {
           try {
-            infos[i] = jpeg_parse(p, b.size);
+            infos[i] = jpeg_parse(p, b.size, parse_);
           } catch (const ScannerError& err) {
             throw ScannerError("ImageDecoder: row " + std::to_string(i) +
                                " of the batch: " + err.what());
@@ -587,6 +720,9 @@ class ImageDecoderKernelGPU : public BatchedKernel {
     if (config_.profiler) {
       config_.profiler->increment("jpeg_gpu_decode_frames", live - host_rows);
       config_.profiler->increment("image_decode_host_rows", host_rows);
+      if (opt_.progressive)
+        config_.profiler->increment("jpeg_gpu_progressive_frames",
+                                    stats.progressive_rows);
       if (opt_.serial_scan_on_device) {
         config_.profiler->increment("jpeg_gpu_sync_frames", stats.sync_rows);
         config_.profiler->increment("jpeg_sync_fallback_rows",
@@ -597,6 +733,7 @@ class ImageDecoderKernelGPU : public BatchedKernel {
 
  private:
   JpegGpuOptions opt_;
+  JpegParseOptions parse_;
 };
 
 }  // namespace

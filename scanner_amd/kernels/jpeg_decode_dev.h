@@ -116,4 +116,50 @@ struct JpegSyncArgs {
 // batch's files without restart markers; failures go to the status words.
 void jpeg_sync_enqueue(const JpegSyncArgs& a, hipStream_t stream);
 
+// ---- progressive files (jpeg_progressive_decode.hip) ----
+// One scan of one file: what a workgroup keeps in LDS.
+struct JpegProgScanDesc {
+  JpegDecGeom g;
+  u32 file;         // its JpegDecFile, and its status words
+  u32 ncomp, comp;  // comp: the component of a single-component scan
+  u32 ss, se, ah, al;
+  u32 pad;
+  u64 coef_off;     // the file's slice of the coefficient workspace, int16s
+  u8 zz2nat[64];
+  // ss == 0: the DC tables of components 0..2; else [0] is the AC table
+  JpegHuff tab[3];
+};
+static_assert(sizeof(JpegProgScanDesc) % 8 == 0,
+              "descriptors are copied as words");
+struct JpegProgGroup {
+  u32 desc;
+  u32 seg0;       // first segment record of the workgroup
+  u32 nseg;       // lanes in use
+  u32 file_seg0;  // index of that segment inside its scan
+};
+struct JpegProgFile {
+  u32 file;  // its JpegDecFile
+  u32 nblk;  // nmcu * blocks_per_mcu
+  u64 coef_off;
+};
+struct JpegProgArgs {
+  JpegDecArgs dec;
+  const JpegProgScanDesc* descs;
+  const JpegProgGroup* groups;  // ordered by scan index, then file
+  const JpegDecSeg* segs;       // first_mcu/mcu_count in the scan's units
+  const JpegProgFile* pfiles;
+  // one word per JpegDecFile, kJpegDecNoError or the scan that failed; the
+  // cause and the segment go to dec.status as for a baseline file
+  u32* fail_scan;
+  i16* coef;  // 64 per block, zeroed by the enqueue
+  u64 coef_count;
+  u32 npfiles, max_nblk;
+};
+// Enqueues everything between the upload and the colour kernel for the
+// batch's progressive files: the memset of the workspace, one launch per
+// scan index k over groups [group0[k], group0[k + 1]), k < nlaunch, and the
+// IDCT. Failures go to the status words.
+void jpeg_prog_enqueue(const JpegProgArgs& a, const u32* group0, u32 nlaunch,
+                       hipStream_t stream);
+
 }  // namespace sca

@@ -26,6 +26,22 @@ one process after a warm-up; each is reported as seconds per batch, median
 and spread (min..max) over --reps timed calls. Prints one JSON line per
 result and, with --md, appends a markdown table. Needs a GPU: there is no
 CPU fallback for a timing.
+
+--progressive measures the progressive decoder instead, on Pillow 4:2:0 files
+of the same images, smooth and noise, saved four ways (baseline or
+progressive, a restart marker per MCU row or none):
+
+  base_rows1/gpu         baseline, device decode: the yardstick
+  prog_rows1/gpu_prog    progressive="decode", every scan on the device, one
+                         lane per restart segment
+  prog_plain/gpu_prog_serial   progressive without restart markers under
+                         serial_scan="device": one lane per scan
+  prog_plain/gpu_prog_host     the same files with the default serial_scan:
+                         decoded on the host inside the call
+  base_plain/gpu         baseline without restart markers, host path, for
+                         scale
+A build without the progressive option (an older commit) runs the baseline
+sides alone, which is how the baseline sides of two commits are compared.
 """
 import argparse
 import io
@@ -63,8 +79,80 @@ def pillow_side(blobs):
     return dt + _core.jpeg_decode_bench(raw, 1, "upload")[0]
 
 
+def progressive_main(args):
+    """The --progressive sides; see the module docstring."""
+    from PIL import Image
+    have_prog = "progressive" in (_core.jpeg_decode_bench.__doc__ or "")
+    _core.init_memory(4 << 30, 8 << 30, [0])
+
+    def save(f, **kw):
+        buf = io.BytesIO()
+        Image.fromarray(f).save(buf, "JPEG", quality=args.quality,
+                                subsampling=2, **kw)
+        return buf.getvalue()
+
+    rows = []
+    for clip in ("smooth", "noise"):
+        fr = frames(clip, args.batch)
+        sides = [("base_rows1", "gpu", [save(f, restart_marker_rows=1)
+                                        for f in fr], {}),
+                 ("base_plain", "gpu", [save(f) for f in fr], {})]
+        if have_prog:
+            rows1 = [save(f, progressive=True, restart_marker_rows=1)
+                     for f in fr]
+            plain = [save(f, progressive=True) for f in fr]
+            dec = dict(progressive="decode")
+            sides += [("prog_rows1", "gpu_prog", rows1, dec),
+                      ("prog_plain", "gpu_prog_serial", plain,
+                       dict(dec, serial_scan="device")),
+                      ("prog_plain", "gpu_prog_host", plain, dec)]
+        secs = [[] for _ in sides]
+        for _, _, blobs, kw in sides:  # warm-up, every side
+            _core.jpeg_decode_bench(blobs, 1, "gpu", **kw)
+        for _ in range(args.reps):  # the sides alternate
+            for k, (_, _, blobs, kw) in enumerate(sides):
+                secs[k].append(_core.jpeg_decode_bench(blobs, 1, "gpu",
+                                                       **kw)[0])
+        for k, (files, mode, blobs, kw) in enumerate(sides):
+            med = statistics.median(secs[k])
+            r = {"files": f"{files}_{clip}", "mode": mode,
+                 "batch": args.batch, "reps": args.reps,
+                 "quality": args.quality,
+                 "bytes_per_file": sum(map(len, blobs)) // len(blobs),
+                 "seconds": {"median": med, "min": min(secs[k]),
+                             "max": max(secs[k])},
+                 "frames_per_s": args.batch / med}
+            if kw:
+                frames_, host_rows, st = _core.jpeg_gpu_decode(
+                    blobs, host_rows=True, stats=True, **kw)
+                r["host_rows"] = host_rows
+                r["progressive_rows"] = st["progressive_rows"]
+                info = _core.jpeg_decode_info(blobs[0], progressive="decode")
+                r["scans"] = len(info["scans"])
+                r["segments_per_file"] = sum(s["segment_count"]
+                                             for s in info["scans"])
+            rows.append(r)
+            print(json.dumps(r), flush=True)
+    _core.destroy_memory()
+    if args.md:
+        with open(args.md, "a") as f:
+            f.write("| files | side | median ms/batch | min..max ms | "
+                    "frames/s | bytes/file | scans | segments/file | host "
+                    "rows |\n|---|---|---|---|---|---|---|---|---|\n")
+            for r in rows:
+                s = {k: v * 1e3 for k, v in r["seconds"].items()}
+                f.write(f"| {r['files']} | {r['mode']} | {s['median']:.3f} | "
+                        f"{s['min']:.3f}..{s['max']:.3f} | "
+                        f"{r['frames_per_s']:.1f} | {r['bytes_per_file']} | "
+                        f"{r.get('scans', '')} | "
+                        f"{r.get('segments_per_file', '')} | "
+                        f"{r.get('host_rows', '')} |\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--progressive", action="store_true",
+                    help="measure the progressive decoder (see above)")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--quality", type=int, default=90)
@@ -76,6 +164,8 @@ def main():
         ap.error("--reps must be >= 5")
     if not _core.have_gpu():
         sys.exit("bench_jpeg_decode needs a GPU")
+    if args.progressive:
+        return progressive_main(args)
     from PIL import Image
     _core.init_memory(4 << 30, 8 << 30, [0])
     sets = {}

@@ -53,6 +53,7 @@ HIP_SOURCES = [
     "kernels/png_encode.hip",
     "kernels/jpeg_decode.hip",
     "kernels/jpeg_sync_decode.hip",
+    "kernels/jpeg_progressive_decode.hip",
     "kernels/mjpeg_index.hip",
     "kernels/color.hip",
     "kernels/optflow.hip",

@@ -720,9 +720,12 @@ PYBIND11_MODULE(_core, m) {
         py::arg("frames"), py::arg("gop") = 16);
   // CPU decode of a packet stream given its per-frame sizes (checks the
   // GPU encoder's output with the CPU decoder alone)
+  // `keyframes`, when given, is the explicit sorted list of key frame
+  // indices and replaces the `gop` period; `want` defaults to every frame.
   m.def("svc_cpu_decode",
         [](py::bytes stream_b, std::vector<u64> sizes, i32 h, i32 w, i32 c,
-           i32 gop) {
+           i32 gop, std::optional<std::vector<i64>> keyframes,
+           std::optional<std::vector<i64>> want_opt) {
           std::string stream = stream_b;
           SCA_CHECK(gop >= 1, "gop must be >= 1");
           VideoMetadata vm;
@@ -735,12 +738,15 @@ PYBIND11_MODULE(_core, m) {
           u64 off = 0;
           std::vector<i64> want;
           for (size_t i = 0; i < sizes.size(); ++i) {
-            if (i % gop == 0) vm.keyframe_indices.push_back((i64)i);
+            if (!keyframes && i % gop == 0)
+              vm.keyframe_indices.push_back((i64)i);
             vm.sample_offsets.push_back(off);
             vm.sample_sizes.push_back(sizes[i]);
             off += sizes[i];
             want.push_back((i64)i);
           }
+          if (keyframes) vm.keyframe_indices = *keyframes;
+          if (want_opt) want = *want_opt;
           SCA_CHECK(off == stream.size(), "sizes do not add up to the stream");
           std::vector<std::vector<u8>> frames;
           svc_decode_cpu((const u8*)stream.data(), stream.size(), vm, want,
@@ -753,7 +759,93 @@ PYBIND11_MODULE(_core, m) {
           return out;
         },
         py::arg("stream"), py::arg("sizes"), py::arg("h"), py::arg("w"),
-        py::arg("c"), py::arg("gop") = 16);
+        py::arg("c"), py::arg("gop") = 16, py::arg("keyframes") = py::none(),
+        py::arg("want") = py::none());
+  // GPU decode of any packet stream, the way the executor calls it.
+  // resident=False: the bytes [offset(first), end of the span's last packet)
+  // go into a pinned CPU-pool buffer and svc_decode_gpu uploads what it
+  // needs (stream_offset = offset(first)). resident=True: the bytes from
+  // offset(first) on are uploaded first and svc_decode_gpu_dev decodes from
+  // them (dev_lo = offset(first)), the span-cache path. Returns the wanted
+  // frames; every buffer it took is back in its pool on return or throw.
+  m.def("svc_gpu_decode",
+        [](py::bytes stream_b, std::vector<u64> sizes, i32 h, i32 w, i32 c,
+           std::vector<i64> keyframes, std::vector<i64> want, bool resident,
+           i64 first) {
+          std::string stream = stream_b;
+          SCA_CHECK(h > 0 && w > 0 && c > 0, "bad frame geometry");
+          VideoMetadata vm;
+          vm.codec = "svc";
+          vm.height = h;
+          vm.width = w;
+          vm.channels = c;
+          vm.frame_type = FrameType::U8;
+          vm.num_frames = (i64)sizes.size();
+          vm.keyframe_indices = keyframes;
+          u64 total = 0;
+          for (u64 sz : sizes) {
+            vm.sample_offsets.push_back(total);
+            vm.sample_sizes.push_back(sz);
+            total += sz;
+          }
+          SCA_CHECK(total == stream.size(),
+                    "sizes do not add up to the stream");
+          i64 n = (i64)sizes.size();
+          if (first < 0) first = 0;
+          SCA_CHECK(first == 0 || first < n, "first beyond stream");
+          size_t fsize = (size_t)h * w * c;
+          py::array_t<u8> out({(i64)want.size(), (i64)h, (i64)w, (i64)c});
+          u8* out_p = out.mutable_data();
+          {
+            py::gil_scoped_release rel;
+            DeviceHandle dev{DeviceType::GPU, 0};
+            std::vector<i64> span = svc_decode_span(vm, want);
+            u64 lo = n > 0 ? vm.sample_offsets[first] : 0;
+            // a span frame the stream does not hold is the decoder's to
+            // reject; here it only must not index past the tables
+            u64 hi = total;
+            if (!resident && !span.empty() && span.back() >= 0 &&
+                span.back() < n)
+              hi = vm.sample_offsets[span.back()] +
+                   vm.sample_sizes[span.back()];
+            if (hi < lo) hi = lo;
+            size_t nb = (size_t)(hi - lo);
+            const u8* src = (const u8*)stream.data() + lo;
+            u8* h_stream = nullptr;
+            u8* d_stream = nullptr;
+            std::vector<Element> elems;
+            try {
+              if (resident) {
+                d_stream = new_buffer(dev, nb ? nb : 1);
+                if (nb) memcpy_buffer(d_stream, dev, src, CPU_DEVICE, nb);
+                elems = svc_decode_gpu_dev(d_stream, lo, vm, want, dev);
+              } else {
+                h_stream = new_buffer(CPU_DEVICE, nb ? nb : 1);
+                std::memcpy(h_stream, src, nb);
+                elems = svc_decode_gpu(h_stream, nb, vm, want, dev, lo);
+              }
+              SCA_CHECK(elems.size() == want.size(),
+                        "svc_gpu_decode: frame count mismatch");
+              // one copy per frame: the frames are allocations of their
+              // own, which memcpy_vec would coalesce when they lie adjacent
+              for (size_t i = 0; i < elems.size(); ++i)
+                memcpy_buffer(out_p + i * fsize, CPU_DEVICE, elems[i].buffer,
+                              dev, fsize);
+            } catch (...) {
+              for (auto& e : elems) delete_buffer(dev, e.buffer);
+              if (d_stream) delete_buffer(dev, d_stream);
+              if (h_stream) delete_buffer(CPU_DEVICE, h_stream);
+              throw;
+            }
+            for (auto& e : elems) delete_buffer(dev, e.buffer);
+            if (d_stream) delete_buffer(dev, d_stream);
+            if (h_stream) delete_buffer(CPU_DEVICE, h_stream);
+          }
+          return out;
+        },
+        py::arg("stream"), py::arg("sizes"), py::arg("h"), py::arg("w"),
+        py::arg("c"), py::arg("keyframes"), py::arg("want"),
+        py::arg("resident") = false, py::arg("first") = 0);
   // The clip is uploaded as ONE contiguous device buffer (frame i at
   // i*nbytes), so an odd nbytes gives misaligned frames. chunk > 0 splits
   // the encode into consecutive calls of `chunk` frames, each predicting its

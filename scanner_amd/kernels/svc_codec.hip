@@ -14,6 +14,7 @@
 // memory at all).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdlib>
 
 #include "../csrc/memory.h"
@@ -217,6 +218,16 @@ __global__ void __launch_bounds__(128)
 // (video/span_cache.h) feed decode without the bytes ever revisiting the
 // host. `up_ev`, when non-null, is an event the upload was recorded on;
 // decode chains wait on it.
+// The span indexes sample_offsets/sample_sizes: reject a frame the stream
+// does not hold before any offset is read or any HIP call is made (same
+// text as svc_decode_cpu).
+static void check_span_in_stream(const VideoMetadata& vm,
+                                 const std::vector<i64>& span) {
+  size_t n = std::min(vm.sample_offsets.size(), vm.sample_sizes.size());
+  for (i64 f : span)
+    SCA_CHECK(f >= 0 && (size_t)f < n, "frame beyond stream");
+}
+
 static std::vector<Element> svc_decode_gpu_impl(
     const u8* d_stream, u64 lo, const VideoMetadata& vm,
     const std::vector<i64>& span, const std::vector<i64>& want,
@@ -339,7 +350,11 @@ static std::vector<Element> svc_decode_gpu_impl(
   }
   SVC_CHECK(hipStreamSynchronize(s));
   for (u8* sc : scratches) delete_buffer(dev, sc);
-  SCA_CHECK(wi == want.size(), "svc gpu decode: not all frames produced");
+  if (wi != want.size()) {
+    // e.g. a frame named twice: hand the outputs back before rejecting
+    for (Element& e : out) delete_buffer(dev, e.buffer);
+    SCA_CHECK(false, "svc gpu decode: not all frames produced");
+  }
   return out;
 }
 
@@ -349,6 +364,7 @@ std::vector<Element> svc_decode_gpu(const u8* stream_host, size_t size,
                                     DeviceHandle dev, u64 stream_offset) {
   std::vector<i64> span = svc_decode_span(vm, want);
   if (span.empty()) return {};
+  check_span_in_stream(vm, span);
   hipStream_t s = (hipStream_t)per_thread_hip_stream();
 
   // Upload the byte range covering the span asynchronously on the main
@@ -389,6 +405,7 @@ std::vector<Element> svc_decode_gpu_dev(const u8* stream_dev, u64 dev_lo,
                                         DeviceHandle dev) {
   std::vector<i64> span = svc_decode_span(vm, want);
   if (span.empty()) return {};
+  check_span_in_stream(vm, span);
   u64 lo = vm.sample_offsets[span.front()];
   u64 hi = vm.sample_offsets[span.back()] + vm.sample_sizes[span.back()];
   SCA_CHECK(lo >= dev_lo, "svc device stream range does not cover span");

@@ -334,10 +334,14 @@ def test_gpu_svc_decode_4k_exact(sc):
 
 
 def test_gpu_svc_decode_multibatch_chain(sc):
-    """A >16-frame GOP forces the chain across multiple GOP-batch kernel
-    launches (register chain state handed over via the scratch buffer);
-    sparse wants make interior frames registers-only."""
+    """Sparse wants over several GOPs make interior frames registers-only.
+    Ingest encodes at GOP 16, so through the engine no chain is longer than
+    one 16-frame launch; the same clip encoded as ONE 40-frame GOP is then
+    decoded directly, which forces the chain across three launches (chain
+    state handed over through the scratch buffer: frames 15 and 31 are not
+    wanted). tests/test_svc_decode_gpu.py covers that path in full."""
     from conftest import make_smooth_video
+    from scanner_amd import _core
     frames = make_smooth_video(n=40, h=120, w=160)
     video = sp.NamedVideoStream(sc, "gmb", frames=frames, codec="svc",
                                 io_packet_size=40)
@@ -348,6 +352,10 @@ def test_gpu_svc_decode_multibatch_chain(sc):
     sc.run(sc.io.Output(g, [out]), sp.PerfParams.manual(4, 8),
            cache_mode=sp.CacheMode.Overwrite, gpu_ids=[0])
     got = np.stack(list(sp.NamedVideoStream(sc, "gmb_out").load()))
+    np.testing.assert_array_equal(got, frames[[0, 7, 18, 19, 33, 39]])
+    stream, sizes = _core.svc_cpu_encode(frames, 40)
+    got = _core.svc_gpu_decode(stream, sizes, 120, 160, 3, [0],
+                               [0, 7, 18, 19, 33, 39])
     np.testing.assert_array_equal(got, frames[[0, 7, 18, 19, 33, 39]])
 
 

@@ -8,7 +8,8 @@ import pytest
 
 import scanner_amd as sp
 from scanner_amd import FrameType, _core, register_python_op
-from conftest import make_smooth_video, make_video
+from conftest import make_smooth_video
+from svc_cases import clip, crafted_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -24,53 +25,6 @@ SHAPES = [
     (2, 1080, 1920, 3),  # 1519 supergroups: more than one scan step
 ]
 CONTENTS = ["smooth", "noise", "constant", "alternate", "widths"]
-
-
-def residual_for_bits(b):
-    """A residual whose zigzag code needs exactly b bits: 0 -> 0, -1 -> 1,
-    2^(b-2) -> 2^(b-1) for b >= 2."""
-    return 0 if b == 0 else (-1 if b == 1 else 1 << (b - 2))
-
-
-def crafted_bits(shape):
-    n = shape[0]
-    ngroups = (int(np.prod(shape[1:])) + 31) // 32
-    f, g = np.mgrid[0:n, 0:ngroups]
-    return (g + f) % 9
-
-
-def crafted_widths_clip(shape, gop):
-    """Group g of frame f is constant and needs exactly (g + f) % 9 bits:
-    a key group holds 128 + r (first residual r, the rest 0), a delta group
-    the previous frame's value + r (every residual r)."""
-    n = shape[0]
-    nbytes = int(np.prod(shape[1:]))
-    bits = crafted_bits(shape)
-    r = np.vectorize(residual_for_bits)(bits)
-    vals = np.zeros(bits.shape, np.int64)
-    for f in range(n):
-        vals[f] = (128 if f % gop == 0 else vals[f - 1]) + r[f]
-    flat = np.repeat(vals % 256, 32, axis=1)[:, :nbytes]
-    return flat.astype(np.uint8).reshape(shape)
-
-
-@functools.lru_cache(maxsize=None)
-def clip(shape, content, gop=16):
-    n, h, w, c = shape
-    if content == "smooth":
-        f = make_smooth_video(n=n, h=h, w=w)[..., :c]
-    elif content == "noise":
-        f = make_video(n=n, h=h, w=w, c=c, seed=11)
-    elif content == "constant":
-        f = np.full(shape, 77, np.uint8)
-    elif content == "alternate":
-        f = np.zeros(shape, np.uint8)
-        f[1::2] = 128
-    else:
-        f = crafted_widths_clip(shape, gop)
-    f = np.ascontiguousarray(f)
-    f.setflags(write=False)
-    return f
 
 
 @functools.lru_cache(maxsize=None)
